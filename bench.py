@@ -26,6 +26,14 @@ the workload's transcripts, 8 batches in flight (round-1 headline; weak scaling)
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 the driver uses
 torch.distributed.run, one rank per GPU.  The time is the max over ranks.
+
+A plain run sets up, warms up, times the K steps and prints the result line: the headline, the
+step's counts and the HIP-event figures of the timed steps themselves.  --full adds what takes
+work of its own or reads the committed profiles: the CPU baseline on the oracle, the K1 traffic /
+rocprof / issue-roofline figures from profiles/, the counts after every warm-up pass, and for
+--config c2 the S2-only and host-buffer legs.  --dump-outputs DIR writes what the last timed step
+computed as DIR/<name>.npy (dump_c3 / dump_c2 below); the inputs are seeded, so two builds can be
+compared array for array.
 """
 import argparse
 import json
@@ -55,7 +63,12 @@ def parse():
     ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="pairs timed on the CPU oracle (rank 0, N=1)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="repeat the CPU sample until this much wall time")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the host CPU share (OMP_NUM_THREADS, else all cores)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the figures read from profiles/ and (c2) the S2-only and "
+                         "host-buffer legs; off: the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-placement", action="store_true", help="skip the S2 + partner placement leg")
     ap.add_argument("--no-kernel-events", action="store_true", help="diagnostic: no timing events in the timed region")
     ap.add_argument("--inflight", type=int, default=None,
@@ -247,7 +260,7 @@ def bench_c2(args, world, rank, gpu, dev, backend):
 
     bytes_per_launch = nr * L + 4 * nr  # 2L bases + 2 x int32 per pair (SURVEY.md §8 d)
     achieved = bytes_per_launch / (k1_ms * 1e-3) / 1e9
-    traffic = pmc_traffic(args.pairs, L)
+    traffic = pmc_traffic(args.pairs, L) if args.full else None
 
     total_pairs = args.pairs * world * args.steps
     value = total_pairs / elapsed
@@ -282,8 +295,11 @@ def bench_c2(args, world, rank, gpu, dev, backend):
             "bytes_per_launch": bytes_per_launch,
         },
     }
+    if args.dump_outputs and rank == 0:
+        dump_c2(args.dump_outputs, bufs[(args.steps - 1) % G], post)
     if post is not None:
         res["partner_placement"] = post.report()
+    if post is not None and args.full:
         # the same steps without the placement (S2 alone), for reference
         run(G, with_placement=False)
         torch.cuda.synchronize(dev)
@@ -297,7 +313,7 @@ def bench_c2(args, world, rank, gpu, dev, backend):
             t_s2 = float(tt.item())
         res["s2_only"] = {"value": round(args.pairs * world * args.steps / t_s2, 1), "unit": "pairs/s",
                           "ms_per_step": round(t_s2 / args.steps * 1e3, 4)}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # the host-buffer API on the same batch: H2D of the reads + the three kernels + D2H of
         # the records (reported beside `value`, never as it)
         al = grp.aligners[0]
@@ -307,7 +323,7 @@ def bench_c2(args, world, rank, gpu, dev, backend):
         dt = time.perf_counter() - t0
         res["pcie_inclusive"] = {"value": round(args.pairs / dt, 1), "unit": "pairs/s",
                                  "note": "af_align_pairs with host buffers (H2D reads, D2H records), 1 call"}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         res["cpu_baseline"] = cpu_baseline(anchor, reads, args, None if args.no_placement else fworld)
     if rank == 0:
         print(json.dumps(res), flush=True)
@@ -333,7 +349,8 @@ def bench_c3(args, world, rank, gpu, dev, backend):
     W = simworld.GenomeWorld(anchor, device=gpu, seed=20251015, scale=args.genome_scale)
     t_gen = time.perf_counter() - t0
     log(f"genome {W.total / 1e9:.2f} Gbp made in {t_gen:.1f} s")
-    subset = genome_subset(W) if rank == 0 and world == 1 and not args.no_cpu else None
+    with_cpu = rank == 0 and world == 1 and args.full and not args.no_cpu
+    subset = genome_subset(W) if with_cpu else None
     t0 = time.perf_counter()
     ref = W.genome_index()
     torch.cuda.synchronize(dev)
@@ -379,8 +396,8 @@ def bench_c3(args, world, rank, gpu, dev, backend):
         t0 = time.perf_counter()
         step()
         torch.cuda.synchronize(dev)
-        log(f"warm-up pass {w}: {time.perf_counter() - t0:.3f} s, "
-            f"{disc.summary() if world == 1 else step_counts}")
+        log(f"warm-up pass {w}: {time.perf_counter() - t0:.3f} s"
+            + (f", {disc.summary() if world == 1 else step_counts}" if args.full else ""))
     free, total = torch.cuda.mem_get_info(dev)
     E = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
     k1 = [[[E(), E()] for _ in range(n_groups)] for _ in range(args.steps)]
@@ -415,7 +432,7 @@ def bench_c3(args, world, rank, gpu, dev, backend):
     bytes_per_launch = k1_bytes / max(1, n_launch)
     k1_launch_ms = k1_ms / max(1, n_launch)
     achieved = bytes_per_launch / (k1_launch_ms * 1e-3) / 1e9
-    traffic = pmc_traffic(bp, L)
+    traffic = pmc_traffic(bp, L) if args.full else None
     if traffic is not None:
         traffic = round(traffic * bytes_per_launch / (bp * (2 * L + 8)))
     res = {
@@ -451,7 +468,7 @@ def bench_c3(args, world, rank, gpu, dev, backend):
                     "stream), S5 (bwa SE, slot 0) then its genome check, and S6 BLAT of every S5 query that can "
                     "be kept (slot 1, from the gathers on; its heavy strands after the check, survivors only), "
                     "compacted to the survivors on slot 0"},
-        "genome_phase": None if world > 1 else genome_phase(summ, phase(3, 4)),
+        "genome_phase": None if world > 1 else genome_phase(summ, phase(3, 4), args.full),
         "kernels_ms": {"seed_filter_per_launch": round(k1_launch_ms, 5), "seed_filter_per_step": round(k1_ms, 4)},
         "roofline": {
             "kernel": "k_seed_filter", "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
@@ -460,15 +477,17 @@ def bench_c3(args, world, rank, gpu, dev, backend):
             "note": "HIP events on K1's stream around each group's back-to-back K1 launches (distinct read "
                     "ranges, no reuse; a group's K1s start once the previous group is done, so no other kernel shares the chip); "
                     "traffic: the committed FETCH_SIZE + WRITE_SIZE passes of this batch shape",
-            "rocprof_check": rocprof_k1(bytes_per_launch, n_launch),
+            "rocprof_check": rocprof_k1(bytes_per_launch, n_launch) if args.full else None,
         },
         "setup_s": {"genome": round(t_gen, 2), "bwa_index": round(t_bwa, 2), "blat_tiles": round(t_idx - t_bwa, 2)},
         "hbm_in_use_gib": round((total - free) / 2**30, 1),
     }
-    issue = issue_roofline()
+    if args.dump_outputs and rank == 0 and world == 1:
+        dump_c3(args.dump_outputs, disc)
+    issue = issue_roofline() if args.full else None
     if issue:
         res["issue_roofline"] = issue
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if with_cpu:
         res["cpu_baseline"] = cpu_baseline_c3(anchor, reads_t, args, subset)
     if rank == 0:
         print(json.dumps(res), flush=True)
@@ -477,14 +496,16 @@ def bench_c3(args, world, rank, gpu, dev, backend):
     tiles.close()
 
 
-def genome_phase(summ, ms):
+def genome_phase(summ, ms, profiles=True):
     """The genome phase's rates: bwa-mem genome reads (S4's both ends + S5's split reads, one
-    seed / region launch) and BLAT queries (S6) over the phase's wall time, and the HBM bytes per
-    genome read of its kernels from the committed FETCH_SIZE pass (profiles/r05/pmc_c3.json)."""
+    seed / region launch) and BLAT queries (S6) over the phase's wall time, and (profiles) the HBM
+    bytes per genome read of its kernels from the committed FETCH_SIZE pass (profiles/r05/pmc_c3.json)."""
     q, n6 = summ.get("queries_s4_s5", 0), summ.get("s6_queries", 0)
     out = {"ms": round(ms, 3), "bwa_genome_reads": q, "blat_queries": n6,
            "bwa_genome_reads_per_s": round(q / (ms * 1e-3), 1) if ms else None,
            "blat_queries_per_s": round(n6 / (ms * 1e-3), 1) if ms else None}
+    if not profiles:
+        return out
     try:
         pm = json.load(open(os.path.join(ROOT, PROF, "pmc_c3.json")))["kernels"]
         per = {k: e["fetch_bytes_per_unit_x2"] for k, e in pm.items() if "fetch_bytes_per_unit_x2" in e}
@@ -494,6 +515,111 @@ def genome_phase(summ, ms):
     except (OSError, ValueError, KeyError):
         pass
     return out
+
+
+DUMP_BUDGET = 64_000_000  # bytes of .npy data per --dump-outputs run
+DUMP_SEED = 20251015
+
+
+def _dump_sample(n, k):
+    """A fixed, seeded, sorted sample of min(n, k) of n rows (the same rows in every run)."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def _dump_fields(rec, prefix, live, out):
+    """The fields of a structured array rec [n, slots] as float64 arrays out[prefix_field]; slots
+    at or past live [n] (never written by the step) read 0."""
+    import numpy as np
+    keep = np.arange(rec.shape[1])[None, :] < live[:, None]
+    for f in rec.dtype.names:
+        v = rec[f].astype(np.float64)
+        out[f"{prefix}_{f}"] = v * keep.reshape(keep.shape + (1,) * (v.ndim - 2))
+
+
+def _dump_s2(out_t, rows, prefix, out):
+    """The S2 records (af_align_pairs' arrays) of the read rows `rows`; CIGAR slots past n_cigar read 0."""
+    import numpy as np
+    import torch
+    idx = torch.from_numpy(rows).to(out_t["flag"].device)
+    got = {k: out_t[k][idx].cpu().numpy() for k in ("flag", "pos", "score", "n_cigar", "hits", "cigar")}
+    live = np.arange(got["cigar"].shape[1])[None, :] < got["n_cigar"][:, None]
+    got["cigar"] = got["cigar"] * live
+    out[f"{prefix}_rows"] = rows.astype(np.float64)
+    for k, v in got.items():
+        out[f"{prefix}_{k}"] = v.astype(np.float64)
+
+
+def _dump_write(path, out):
+    import numpy as np
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_BUDGET:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget")
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    print(f"[bench] {len(out)} arrays, {total / 1e6:.1f} MB written to {path}", file=sys.stderr, flush=True)
+
+
+def dump_c3(path, disc):
+    """What the last pass of discover.CandidateDiscovery.run left for its consumers, as float64
+    .npy files (every value is an integer below 2^53, so the copies are exact):
+      s2_*       S2's records (flag, pos, score, n_cigar, hits, cigar) of a seeded sample of read
+                 rows, and s2q_* of the read rows behind a seeded sample of the S4 / S5 queries;
+      q_rows, q_nrec   every S4 / S5 query's read row and SAM record count; grec_*: the records
+                 (genome.REC_DTYPE) of the same query sample;
+      s6_src, s6_len, s6_nrows   every S6 query (S5's survivors): its S5 query, length and BLAT
+                 row count; psl_*: the kept rows (blat.PSL_DTYPE) of a seeded sample of them;
+      counts     [queries, S6 queries, rows in the spill pool].
+    The spill pool's rows are left out: their order is the order of the kernel's atomics."""
+    import numpy as np
+    import torch
+
+    from anchored_fusion_amd import blat, genome
+    torch.cuda.synchronize(disc.dev)
+    out = {}
+    nr = 2 * disc.n_pairs
+    _dump_s2(disc.out, _dump_sample(nr, 32768), "s2", out)
+    nq = min(int(disc.n_q.item()), disc.qcap)
+    q_rows = disc.q_rows[:nq].cpu().numpy()
+    q_nh = disc.q_nh[:nq].cpu().numpy()
+    out["q_rows"], out["q_nrec"] = q_rows.astype(np.float64), q_nh.astype(np.float64)
+    qs = _dump_sample(nq, 4096)
+    _dump_s2(disc.out, q_rows[qs].astype(np.int64), "s2q", out)
+    rb = genome.MAX_REC * genome.REC_DTYPE.itemsize
+    recs = disc.q_recs[:nq * rb].view(nq, rb)[torch.from_numpy(qs).to(disc.dev)].cpu().numpy()
+    out["grec_query"] = qs.astype(np.float64)
+    _dump_fields(recs.view(genome.REC_DTYPE).reshape(len(qs), genome.MAX_REC), "grec", q_nh[qs], out)
+    n6 = int(disc.s6["n"].item())
+    t_nh = disc.t_nh[:n6].cpu().numpy()
+    out["s6_src"] = disc.s6["src"][:n6].cpu().numpy().astype(np.float64)
+    out["s6_len"] = disc.s6["lens"][:n6].cpu().numpy().astype(np.float64)
+    out["s6_nrows"] = t_nh.astype(np.float64)
+    ts = _dump_sample(n6, 1024)
+    pb = blat.MAX_ROWS * blat.PSL_DTYPE.itemsize
+    rows = disc.t_rows[:n6 * pb].view(n6, pb)[torch.from_numpy(ts).to(disc.dev)].cpu().numpy()
+    out["psl_s6_query"] = ts.astype(np.float64)
+    _dump_fields(rows.view(blat.PSL_DTYPE).reshape(len(ts), blat.MAX_ROWS), "psl",
+                 np.minimum(t_nh[ts], blat.MAX_ROWS), out)
+    out["counts"] = np.array([nq, n6, int(disc.t_spill["n"].item())], dtype=np.float64)
+    _dump_write(path, out)
+
+
+def dump_c2(path, bufs, post):
+    """The last timed batch's S2 records (a seeded sample of read rows) and, with the placement,
+    the last group's tail count and how many of them were placed (the tails are appended in the
+    order of the kernel's atomics, so their rows are not comparable one by one)."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    out = {}
+    _dump_s2(bufs, _dump_sample(int(bufs["flag"].numel()), 65536), "s2", out)
+    if post is not None:
+        n_t = min(int(post.nt_last.item()), post.cap)
+        out["tails"] = np.array([n_t, int((post.last["nh"][:n_t] > 0).sum().item())], dtype=np.float64)
+    _dump_write(path, out)
 
 
 def genome_subset(W, flank=250_000):
