@@ -259,6 +259,8 @@ struct GHeavy {
     int64_t cap_reads, cap_ch, cap_sd;
     int32_t min_chains;               // 0: every read extended by its own wave
 };
+// mem_chain's sorted-array mode (bwa_genome.hip g_mem_chain) holds at most this many chains
+constexpr int AF_G_ARR = 1392;
 // per-call pools and counters of the genome kernels (per context)
 struct GWork {
     GIv *iv;                    // intervals of every read (G1)
@@ -287,6 +289,9 @@ struct GWork {
     uint8_t *g2_flag = nullptr;
     unsigned long long *g2_list_n = nullptr, *g2_list_next = nullptr;
     int32_t g2_first_occ = 0;
+    // the array mode's chain limit (tests: env AF_G_CHAIN_ARR -- 0 every read on the kbtree, a small
+    // count most reads restarted there)
+    int32_t chain_arr = AF_G_ARR;
 };
 size_t af_g1_slot_bytes();
 size_t af_g2_slot_bytes();
@@ -308,6 +313,8 @@ hipError_t af_launch_genome_pe(const DevGenome &G, const uint8_t *reads, int32_t
                                const GWork &w, const S2Work &sw, uint8_t *g2_scratch, int n_waves, uint8_t *zscratch,
                                af_grec *recs, int32_t *n_rec, hipStream_t s);
 hipError_t af_launch_s2_pestat(const S2Work &w, int32_t max_ins, hipStream_t s);
+// test hook af_debug_kbtree (bwa_genome.hip), store 0: the kbtree over the S2 store (s2.hip)
+hipError_t af_launch_debug_kbtree_s2(const int64_t *pos, int n, int32_t *lower, int32_t *order, int32_t *count);
 
 // launch helpers (defined in the .hip files)
 // ctrl (AF_CTRL_BYTES, one 128-B line per word, no memsets on the hot path):

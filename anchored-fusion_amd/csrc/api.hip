@@ -548,6 +548,7 @@ GWork genome_work(af_ctx *c, int64_t n_reads) {
     w.pe.min_windows = c->g_pe.cnt ? c->g_pe_min : 0;
     w.g2_list = c->g2_list; w.g2_flag = c->g2_flag; w.g2_list_n = c->g_iv_fill + 4; w.g2_list_next = c->g_iv_fill + 5;
     w.g2_first_occ = c->g2_flag ? c->g2_first_occ : 0;
+    if (const char *ca = getenv("AF_G_CHAIN_ARR")) w.chain_arr = std::max(0, std::min(AF_G_ARR, atoi(ca)));  // read per call
     w.stats = c->g_stats;
     return w;
 }

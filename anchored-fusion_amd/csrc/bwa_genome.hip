@@ -26,7 +26,7 @@
 // per-wave global scratch (L2 / Infinity Cache resident for the common short lists); the DP
 // rows, query and target windows in LDS (ksw_dp.h g_dp).  Caps equal the oracle's AFO_G_MAX_*;
 // a read past one is reported unmapped with AF_FLAG_MEM_OVERFLOW, counted in the call's stats.
-#include "bwa_dev.h"
+#include "bwa_mem_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -50,12 +50,11 @@ __device__ __forceinline__ uint32_t gp_rt() { return (uint32_t)wall_clock64(); }
 #define GPROF(...)
 #endif
 
-constexpr int G_KB_T = 5, G_KB_MAXK = 2 * G_KB_T - 1;
 constexpr int G_KB_NODES = AF_G_MAX_CHAIN / 2 + 64;  // t = 5: >= 4 keys per non-root node
 
 struct GSeed { int64_t rbeg; int32_t qbeg, len; };   // mem_seed_t (score = len)
 struct GChain { int64_t pos; int32_t n, first, rid, w, kept, seed0; };  // mem_chain_t
-struct GKb { int16_t n, internal; int16_t key[G_KB_MAXK]; int16_t ptr[G_KB_MAXK + 1]; };
+typedef KbNode<int16_t> GKb;
 
 // ================================================================== FM index (bwt.c)
 // bwt_occ4: occurrences of A/C/G/T in the BWT rows [0, i).  A 128-row block holds its four
@@ -735,111 +734,23 @@ struct GChainLds {
 
 static_assert(sizeof(GChainLds) <= sizeof(G2Box) * G2_BOXES, "mem_chain's LDS set fits the boxes");
 
-// ---- klib kbtree (t = 5) over chain indices keyed by chain pos; lane 0 (oracle kb_*)
+// ---- the kbtree's store (bwa_mem_dev.h kb_*): the first G_KB_LDS nodes and G_POS_LDS keys in LDS,
+// the rest in the wave's global scratch; root and node count in registers
 struct GTree {
+    typedef int16_t Idx;
+    typedef int64_t Pos;
+    static constexpr int DEPTH = 16;  // (depth <= 8 for 8192 keys at t = 5)
     GKb *node_l, *node_g;
-    int nn, root;
+    int nn, rt;
     const GChain *ch;
     const int64_t *pos_l;
     __device__ GKb &nd(int i) const { return i < G_KB_LDS ? node_l[i] : node_g[i]; }
     __device__ int64_t pos(int x) const { return x < G_POS_LDS ? pos_l[x] : ch[x].pos; }
+    __device__ int root() const { return rt; }
+    __device__ void set_root(int i) { rt = i; }
+    __device__ int alloc() { return nn++; }
+    __device__ bool full() const { return nn + 16 >= G_KB_NODES; }  // one insertion adds at most depth + 1 nodes
 };
-__device__ __forceinline__ int gkb_cmp(const GTree &b, int x, int64_t kpos) {
-    const int64_t a = b.pos(x);
-    return (kpos < a) - (a < kpos);
-}
-__device__ int gkb_getp_aux(const GTree &b, const GKb &x, int64_t kpos, int *r) {
-    int tr, *rr, begin = 0, end = x.n;
-    if (x.n == 0) return -1;
-    rr = r ? r : &tr;
-    while (begin < end) {
-        const int mid = (begin + end) >> 1;
-        if (gkb_cmp(b, x.key[mid], kpos) < 0) begin = mid + 1;
-        else end = mid;
-    }
-    if (begin == x.n) { *rr = 1; return x.n - 1; }
-    if ((*rr = -gkb_cmp(b, x.key[begin], kpos)) < 0) --begin;
-    return begin;
-}
-__device__ int gkb_new(GTree &b, int internal) {
-    GKb &z = b.nd(b.nn);
-    z.n = 0; z.internal = (int16_t)internal;
-    return b.nn++;
-}
-__device__ int gkb_lower(const GTree &b, int64_t kpos) {
-    int r = 0, lower = -1, xi = b.root;
-    while (xi >= 0) {
-        const GKb &x = b.nd(xi);
-        const int i = gkb_getp_aux(b, x, kpos, &r);
-        if (i >= 0 && r == 0) return x.key[i];
-        if (i >= 0) lower = x.key[i];
-        if (!x.internal) return lower;
-        xi = x.ptr[i + 1];
-    }
-    return lower;
-}
-__device__ void gkb_split(GTree &b, int xi, int i, int yi) {
-    const int zi = gkb_new(b, b.nd(yi).internal);
-    GKb &x = b.nd(xi), &y = b.nd(yi), &z = b.nd(zi);
-    z.n = G_KB_T - 1;
-    for (int u = 0; u < G_KB_T - 1; ++u) z.key[u] = y.key[G_KB_T + u];
-    if (y.internal)
-        for (int u = 0; u < G_KB_T; ++u) z.ptr[u] = y.ptr[G_KB_T + u];
-    y.n = G_KB_T - 1;
-    for (int u = x.n; u >= i + 1; --u) x.ptr[u + 1] = x.ptr[u];
-    x.ptr[i + 1] = (int16_t)zi;
-    for (int u = x.n - 1; u >= i; --u) x.key[u + 1] = x.key[u];
-    x.key[i] = y.key[G_KB_T - 1];
-    ++x.n;
-}
-__device__ bool gkb_putp(GTree &b, int k) {
-    const int64_t kpos = b.pos(k);
-    int xi = b.root;
-    if (b.nn + 16 >= G_KB_NODES) return false;  // one insertion adds at most depth + 1 nodes
-    if (b.nd(xi).n == G_KB_MAXK) {
-        const int si = gkb_new(b, 1);
-        b.nd(si).ptr[0] = (int16_t)xi;
-        b.root = si;
-        gkb_split(b, si, 0, xi);
-        xi = si;
-    }
-    for (;;) {  // __kb_putp_aux, iteratively
-        GKb &x = b.nd(xi);
-        if (!x.internal) {
-            const int i = gkb_getp_aux(b, x, kpos, nullptr);
-            for (int u = x.n - 1; u >= i + 1; --u) x.key[u + 1] = x.key[u];
-            x.key[i + 1] = (int16_t)k;
-            ++x.n;
-            return true;
-        }
-        int i = gkb_getp_aux(b, x, kpos, nullptr) + 1;
-        if (b.nd(x.ptr[i]).n == G_KB_MAXK) {
-            gkb_split(b, xi, i, x.ptr[i]);
-            if (gkb_cmp(b, b.nd(xi).key[i], kpos) < 0) ++i;  // klib: cmp(*k, key[i]) > 0, k past the promoted key
-        }
-        xi = b.nd(xi).ptr[i];
-    }
-}
-// in-order traversal into order[] (iterative; depth <= 8 for 8192 keys at t = 5)
-__device__ int gkb_traverse(const GTree &b, int32_t *order) {
-    int stk_node[16], stk_i[16], top = 1, n = 0;
-    stk_node[0] = b.root; stk_i[0] = 0;
-    while (top > 0) {
-        const int xi = stk_node[top - 1];
-        const int i = stk_i[top - 1];
-        const GKb &x = b.nd(xi);
-        if (!x.internal) {
-            for (int u = 0; u < x.n; ++u) order[n++] = x.key[u];
-            --top;
-            continue;
-        }
-        if (i > x.n) { --top; continue; }
-        stk_i[top - 1] = i + 1;
-        if (i > 0) order[n++] = x.key[i - 1];
-        stk_node[top] = x.ptr[i]; stk_i[top] = 0; ++top;
-    }
-    return n;
-}
 
 // test_and_merge (oracle test_and_merge), lane 0: 1 merged / contained, 0 not, -1 overflow
 // (hot: the first nhot chains' end seeds in LDS; r_first: chain ci's pos, its first seed's rbeg)
@@ -860,13 +771,11 @@ __device__ int g_test_and_merge(const G2Scr &S, GChainHot *hot, int nhot, int ci
         q_first = first.qbeg; len_first = first.len; q_last = last.qbeg; len_last = last.len;
         crid = c.rid; cn = c.n;
     }
-    (void)len_first;
-    const int64_t qend = (int64_t)q_last + len_last, rend = r_last + len_last;
     if (rid != crid) return 0;
-    if (p.qbeg >= q_first && p.qbeg + p.len <= qend && p.rbeg >= r_first && p.rbeg + p.len <= rend) return 1;
-    if ((r_last < l_pac || r_first < l_pac) && p.rbeg >= l_pac) return 0;
-    const int64_t x = p.qbeg - q_last, y = p.rbeg - r_last;
-    if (y >= 0 && x - y <= w && y - x <= w && x - len_last < max_chain_gap && y - len_last < max_chain_gap) {
+    const int m = chain_merge_test(GSeed{r_first, q_first, len_first}, GSeed{r_last, q_last, len_last}, p, l_pac, w,
+                                   max_chain_gap);
+    if (m == MERGE_CONTAINED) return 1;
+    if (m == MERGE_APPEND) {
         if (*npool >= AF_G_MAX_OCC) return -1;
         const int k = (*npool)++;
         S.pool[k] = p;
@@ -889,10 +798,8 @@ __device__ int g_test_and_merge(const G2Scr &S, GChainHot *hot, int nhot, int ci
 // wave searches it (two ballots) and shifts it open for an insertion, instead of lane 0 walking
 // tree nodes.  A second chain at an existing pos (whose place among the equal keys depends on the
 // tree's shape) or chain G_ARR + 1 restarts the read on the kbtree.
-constexpr int G_ARR = 1392, G_CH_ARR = 64;
-// the array mode's chain limit (tests: env AF_G_CHAIN_ARR -- 0 every read on the kbtree, a small
-// count most reads restarted there)
-__device__ int g_chain_arr = G_ARR;
+// (GWork.chain_arr: the array mode's chain limit of a call, at most G_ARR)
+constexpr int G_ARR = AF_G_ARR, G_CH_ARR = 64;
 struct GChainArr {
     int64_t key[G_ARR];
     int16_t id[G_ARR];
@@ -917,7 +824,7 @@ __device__ __forceinline__ int g_arr_rank(const int64_t *key, int n, int64_t kpo
 // seeds compacted in S.seed), -1 on overflow.  The wave gathers 64 SA rows at a time; the array
 // mode takes each seed on the whole wave, the kbtree mode on lane 0.
 __device__ int g_mem_chain(const DevGenome &G, const G2Scr &S, const GIv *iv, int niv, const af_params &p,
-                           const GOpt &o, int lane) {
+                           const GOpt &o, const GWork &w, int lane) {
     G2Lds &E = g_g2;
     GChainLds &C = *reinterpret_cast<GChainLds *>(g_box);
     GChainArr &A = *reinterpret_cast<GChainArr *>(g_box);
@@ -929,8 +836,8 @@ __device__ int g_mem_chain(const DevGenome &G, const G2Scr &S, const GIv *iv, in
         by_arr = arr;
         nch = 0; npool = 0; ovf = false;
         bool restart = false;
-        tree.nn = 0; tree.root = 0;
-        if (!arr && lane == 0) tree.root = gkb_new(tree, 0);
+        tree.nn = 0; tree.rt = 0;
+        if (!arr && lane == 0) tree.set_root(kb_new(tree, 0));
         int32_t *const ridv = arr ? A.rid : C.rid;
         for (int i = 0; i < niv && !ovf && !restart; ++i) {
             const GIv v = iv[i];
@@ -968,7 +875,7 @@ __device__ int g_mem_chain(const DevGenome &G, const G2Scr &S, const GIv *iv, in
                             if (r == 0 && kl == s.rbeg) { restart = true; break; }  // a second chain at this pos
                         }
                         if (r) continue;
-                        if (nch >= g_chain_arr) { restart = true; break; }
+                        if (nch >= w.chain_arr) { restart = true; break; }
                         if (nch >= AF_G_MAX_CHAIN || npool >= AF_G_MAX_OCC) { ovf = true; break; }
                         // open entry `at`: move [at, nch) up by one, the top 64 first
                         for (int top = nch - 1; top >= at; top -= 64) {
@@ -1006,7 +913,7 @@ __device__ int g_mem_chain(const DevGenome &G, const G2Scr &S, const GIv *iv, in
                         if (rid < 0) continue;
                         bool to_add = false;
                         if (nch) {
-                            const int lower = gkb_lower(tree, s.rbeg);
+                            const int lower = kb_lower(tree, s.rbeg);
                             if (lower < 0) to_add = true;
                             else {
                                 const int r = g_test_and_merge(S, C.ch, G_CH_LDS, lower, tree.pos(lower), s, rid, G.l_pac,
@@ -1026,7 +933,7 @@ __device__ int g_mem_chain(const DevGenome &G, const G2Scr &S, const GIv *iv, in
                             if (nch < G_CH_LDS)
                                 C.ch[nch] = GChainHot{s.rbeg, rid, 1, (int16_t)s.qbeg, (int16_t)s.len, (int16_t)s.qbeg,
                                                       (int16_t)s.len, (int16_t)kk, 0};
-                            if (!gkb_putp(tree, nch)) { ovf = true; break; }
+                            if (!kb_putp(tree, nch)) { ovf = true; break; }
                             ++nch;
                         }
                     }
@@ -1046,7 +953,7 @@ __device__ int g_mem_chain(const DevGenome &G, const G2Scr &S, const GIv *iv, in
             no = nch;
             __threadfence_block();
             wave_sync();
-        } else if (lane == 0) no = gkb_traverse(tree, S.order);
+        } else if (lane == 0) no = kb_traverse(tree, S.order);
     }
     if (lane == 0 && !ovf) {
         int ns = 0;
@@ -1063,26 +970,6 @@ __device__ int g_mem_chain(const DevGenome &G, const G2Scr &S, const GIv *iv, in
     return ovf ? -1 : E.misc[1];
 }
 
-__device__ int g_chain_weight(const G2Scr &S, const GChain &c) {
-    const GSeed *sd = S.seed + c.seed0;
-    int64_t end = 0;
-    int w = 0, tmp;
-    for (int j = 0; j < c.n; ++j) {
-        const GSeed s = sd[j];
-        if (s.qbeg >= end) w += s.len;
-        else if (s.qbeg + s.len > end) w += (int)(s.qbeg + s.len - end);
-        end = end > s.qbeg + s.len ? end : s.qbeg + s.len;
-    }
-    tmp = w; w = 0; end = 0;
-    for (int j = 0; j < c.n; ++j) {
-        const GSeed s = sd[j];
-        if (s.rbeg >= end) w += s.len;
-        else if (s.rbeg + s.len > end) w += (int)(s.rbeg + s.len - end);
-        end = end > s.rbeg + s.len ? end : s.rbeg + s.len;
-    }
-    w = w < tmp ? w : tmp;
-    return w < 1 << 30 ? w : (1 << 30) - 1;
-}
 struct GLtFlt {
     __device__ bool operator()(const GChain &a, const GChain &b) const { return a.w > b.w; }
 };
@@ -1095,12 +982,12 @@ struct GKeyFlt {  // w << 32 | index: GLtFlt on the keys
 // scan's first breaking chain found by a ballot, so `first` is set exactly for the overlapping
 // kept chains the sequential scan visits); klib's introsort (its tie order is bwa's) and the
 // order-preserving compaction run as in the oracle.
-__device__ int g_chain_flt(const G2Scr &S, int n_chn, const af_params &p, const GOpt &o, int lane) {
+__device__ int g_chain_flt(const G2Scr &S, int n_chn, const af_params &p, const GOpt &o, const GWork &w, int lane) {
     GChain *a = S.ch2;
     if (n_chn == 0) return 0;
     for (int i = lane; i < n_chn; i += 64) {
         GChain c = a[i];
-        c.first = -1; c.kept = 0; c.w = g_chain_weight(S, c);
+        c.first = -1; c.kept = 0; c.w = chain_weight(S.seed + c.seed0, c.n);
         a[i] = c;
     }
     wave_sync();
@@ -1166,7 +1053,7 @@ __device__ int g_chain_flt(const G2Scr &S, int n_chn, const af_params &p, const 
     __threadfence_block();
     wave_sync();
     auto pack = [&](int i) -> uint32_t { return (uint32_t)cb[i] | (uint32_t)ce[i] << 9 | (uint32_t)cw[i] << 18; };
-    bool grp = lds && g_chain_arr > 0;  // (AF_G_CHAIN_ARR=0, a test mode: the kbtree and the chunk scan)
+    bool grp = lds && w.chain_arr > 0;  // (AF_G_CHAIN_ARR=0, a test mode: the kbtree and the chunk scan)
     int ng = 1;
     if (lane == 0) {
         a[0].kept = 3; kp[0] = pack(0); kf[0] = -1;
@@ -1547,20 +1434,8 @@ static_assert(sizeof(G2Box) * G2_BOXES >= 16 * AF_G_MAX_REG, "the boxes hold 16 
 static_assert(sizeof(GReg) == 64, "regions move as 4 x 16 B");
 // lists this long or longer are sorted on the wave by rank (wave_rank_sort), shorter by lane 0
 constexpr int G_RANK_MIN = 24;
-struct GKeyRe {  // re << 10 | index (mem_sort_dedup_patch's sort by re)
-    __device__ bool operator()(uint64_t a, uint64_t b) const { return (a >> 10) < (b >> 10); }
-};
-struct GKey16 { int64_t x; int32_t y; int32_t z; };
-struct GKeyArs {  // x = rb, y = score, z = qb << 16 | index: score desc, rb, qb
-    __device__ bool operator()(const GKey16 &a, const GKey16 &b) const {
-        return a.y > b.y || (a.y == b.y && (a.x < b.x || (a.x == b.x && (a.z >> 16) < (b.z >> 16))));
-    }
-};
-struct GKeyHash {  // x = hash, y = score, z = index: score desc, hash (mark_primary_se)
-    __device__ bool operator()(const GKey16 &a, const GKey16 &b) const {
-        return a.y > b.y || (a.y == b.y && (uint64_t)a.x < (uint64_t)b.x);
-    }
-};
+typedef KeyRe<10> GKeyRe;    // re << 10 | index
+typedef KeyArs<16> GKeyArs;  // z = qb << 16 | index
 // a[k] = old a[from(k)] for k < m (wave)
 template <class F>
 __device__ __forceinline__ void g_regs_gather(GReg *a, GReg *tmp, int m, F from, int lane) {
@@ -1668,18 +1543,18 @@ __device__ int g_dedup_patch(const DevGenome &G, const af_params &p, const GOpt 
         }
     }
     // the live regions (in order) sorted by (score desc, rb, qb); equal neighbours dropped
-    GKey16 *k2 = reinterpret_cast<GKey16 *>(g_box);
+    Key16 *k2 = reinterpret_cast<Key16 *>(g_box);
     int m = 0;
     for (int i0 = 0; i0 < n; i0 += 64) {
         const int i = i0 + lane;
         GReg x;
         const bool live = i < n && ((x = a[i]), x.qe > x.qb);
         const uint64_t lm = __ballot(live);
-        if (live) k2[m + lanes_below(lm, lane)] = GKey16{x.rb, x.score, x.qb << 16 | i};
+        if (live) k2[m + lanes_below(lm, lane)] = Key16{x.rb, x.score, x.qb << 16 | i};
         m += __builtin_popcountll(lm);
     }
     wave_sync();
-    if (m < G_RANK_MIN || !wave_rank_sort(k2, m, GKeyArs(), reinterpret_cast<GKey16 *>(tmp), lane)) {
+    if (m < G_RANK_MIN || !wave_rank_sort(k2, m, GKeyArs(), reinterpret_cast<Key16 *>(tmp), lane)) {
         if (lane == 0) ks_introsort(k2, m, GKeyArs());
         wave_sync();
     }
@@ -1690,12 +1565,12 @@ __device__ int g_dedup_patch(const DevGenome &G, const af_params &p, const GOpt 
     for (int i0 = 0; i0 < m; i0 += 64) {
         const int i = i0 + lane;
         bool keep = false;
-        GKey16 c{0, 0, 0};
+        Key16 c{0, 0, 0};
         if (i < m) {
             c = k2[i];
             keep = i == 0;
             if (i > 0) {
-                const GKey16 d = k2[i - 1];
+                const Key16 d = k2[i - 1];
                 keep = !(c.y == d.y && c.x == d.x && (c.z >> 16) == (d.z >> 16));
             }
         }
@@ -1871,11 +1746,11 @@ __global__ __launch_bounds__(64, 2) void k_g_regions(DevGenome G, const uint8_t 
         if (!ovf && l >= p.min_seed_len && niv > 0) {
             g_load_read(reads, r, stride, l, lane);
             g_iv_sort(w.iv + w.iv_off[r], niv, reinterpret_cast<GIv *>(S.seed), lane);
-            const int nch0 = g_mem_chain(G, S, w.iv + w.iv_off[r], niv, p, o, lane);
+            const int nch0 = g_mem_chain(G, S, w.iv + w.iv_off[r], niv, p, o, w, lane);
             GPROF(gp_c[1] = clock64(); gp_n[0] = nch0;)
             if (nch0 < 0) ovf = true;
             else {
-                const int nch = g_chain_flt(S, nch0, p, o, lane);
+                const int nch = g_chain_flt(S, nch0, p, o, w, lane);
                 GPROF(gp_c[2] = clock64(); gp_n[1] = nch;)
                 if (w.hv.min_chains > 0 && nch >= w.hv.min_chains) deferred = g_defer_heavy(w, S, r, nch, lane);
                 if (!deferred) {
@@ -1994,15 +1869,15 @@ __global__ __launch_bounds__(64, 2) void k_g_heavy(DevGenome G, const uint8_t *_
 // regions' query spans, scores and subs in LDS (the boxes' space); tmp: n regions of scratch
 __device__ void g_mark_primary_w(GReg *a, int n, int64_t id, GReg *tmp, int lane) {
     if (n == 0) return;
-    GKey16 *k = reinterpret_cast<GKey16 *>(g_box);
+    Key16 *k = reinterpret_cast<Key16 *>(g_box);
     for (int i = lane; i < n; i += 64) {
         const uint64_t h = hash_64((uint64_t)(id + i));
         a[i].sub = 0; a[i].secondary = -1; a[i].hash = h;
-        k[i] = GKey16{(int64_t)h, a[i].score, i};
+        k[i] = Key16{(int64_t)h, a[i].score, i};
     }
     wave_sync();
-    if (n < G_RANK_MIN || !wave_rank_sort(k, n, GKeyHash(), reinterpret_cast<GKey16 *>(tmp), lane)) {
-        if (lane == 0) ks_introsort(k, n, GKeyHash());
+    if (n < G_RANK_MIN || !wave_rank_sort(k, n, KeyHash(), reinterpret_cast<Key16 *>(tmp), lane)) {
+        if (lane == 0) ks_introsort(k, n, KeyHash());
         wave_sync();
     }
     g_regs_gather(a, tmp, n, [&](int j) { return k[j].z; }, lane);
@@ -2019,14 +1894,9 @@ __device__ void g_mark_primary_w(GReg *a, int n, int64_t id, GReg *tmp, int lane
             for (kk = 0; kk < nz; ++kk) {
                 const int j = z[kk];
                 const int qbj = span[j] >> 16, qej = span[j] & 0xffff;
-                const int b_max = qbj > qbi ? qbj : qbi;
-                const int e_min = qej < qei ? qej : qei;
-                if (e_min > b_max) {
-                    const int min_l = qei - qbi < qej - qbj ? qei - qbi : qej - qbj;
-                    if ((float)(e_min - b_max) >= (float)min_l * 0.5f) {
-                        if (sub[j] == 0) sub[j] = score[i];
-                        break;
-                    }
+                if (q_overlap_half(qbj, qej, qbi, qei)) {
+                    if (sub[j] == 0) sub[j] = score[i];
+                    break;
                 }
             }
             if (kk == nz) z[nz++] = i;
@@ -2215,34 +2085,6 @@ __global__ __launch_bounds__(64, 2) void k_g_se(DevGenome G, const uint8_t *__re
 }
 
 // ==================================================================== paired end (S4)
-__device__ __forceinline__ int g_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist) {
-    const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-    const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-    *dist = p2 > b1 ? p2 - b1 : b1 - p2;
-    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
-__device__ int g_cal_sub(const GReg *a, int n, int msl, int asc) {
-    int j;
-    for (j = 1; j < n; ++j) {
-        const int b_max = a[j].qb > a[0].qb ? a[j].qb : a[0].qb;
-        const int e_min = a[j].qe < a[0].qe ? a[j].qe : a[0].qe;
-        if (e_min > b_max) {
-            const int min_l = a[j].qe - a[j].qb < a[0].qe - a[0].qb ? a[j].qe - a[j].qb : a[0].qe - a[0].qb;
-            if ((float)(e_min - b_max) >= (float)min_l * 0.5f) break;
-        }
-    }
-    return j < n ? a[j].score : msl * asc;
-}
-__device__ __forceinline__ int g_chunk_of(const S2Work &w, int64_t pp) {
-    int lo = 0, hi = *w.n_chunks;  // cstart[lo] <= pp < cstart[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (w.cstart[mid] <= pp) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // mem_pestat's insert sizes (one lane per pair) into the chunks' histograms
 __global__ void k_g_pe_hist(const int32_t *__restrict__ n_pairs_ptr, int64_t cap, int64_t l_pac, af_params p, GOpt o,
                             GWork w, S2Work sw) {
@@ -2252,13 +2094,13 @@ __global__ void k_g_pe_hist(const int32_t *__restrict__ n_pairs_ptr, int64_t cap
         const int n0 = w.reg_n[2 * pp], n1 = w.reg_n[2 * pp + 1];
         if (n0 <= 0 || n1 <= 0) continue;
         const GReg *a0 = w.reg + w.reg_off[2 * pp], *a1 = w.reg + w.reg_off[2 * pp + 1];
-        if ((double)g_cal_sub(a0, n0, p.min_seed_len, p.a) > 0.8 * a0[0].score) continue;
-        if ((double)g_cal_sub(a1, n1, p.min_seed_len, p.a) > 0.8 * a1[0].score) continue;
+        if ((double)cal_sub(a0, n0, p.min_seed_len, p.a) > 0.8 * a0[0].score) continue;
+        if ((double)cal_sub(a1, n1, p.min_seed_len, p.a) > 0.8 * a1[0].score) continue;
         if (a0[0].rid != a1[0].rid) continue;
         int64_t is;
-        const int dir = g_infer_dir(l_pac, a0[0].rb, a1[0].rb, &is);
+        const int dir = infer_dir(l_pac, a0[0].rb, a1[0].rb, &is);
         if (is && is <= o.max_ins) {
-            const int c = g_chunk_of(sw, pp);
+            const int c = chunk_of(sw, pp);
             atomicAdd(&sw.ghist[((int64_t)c * 4 + dir) * (o.max_ins + 1) + is], 1);
         }
     }
@@ -2269,63 +2111,24 @@ struct GPeLds {
     uint8_t q[2][AF_MAX_READ + 16];
     uint8_t rq[AF_MAX_READ + 16];
     uint8_t rq2[AF_MAX_READ + 16];
-    uint8_t tw[2048];
+    uint8_t tw[PE_TW];
     int32_t na[2], nb[2], ovf[2], len[2], misc[8];
 };
 __shared__ GPeLds g_gpe;
 
-// ksw_align2 with KSW_XSUBO | KSW_XSTART (oracle ksw_align2)
-__device__ void g_ksw_align2(const uint8_t *q, int qlen, const uint8_t *target, int tlen, int P, int minsc,
-                             const af_params &p, int &score, int &te, int &qe, int &tb, int &qb, int lane) {
-    GPeLds &E = g_gpe;
-    const SwRes r = ksw_pass_any(q, qlen, target, tlen, -1, P, p, 0x10000, lane);
-    score = r.score; te = r.te; qe = r.qe; tb = -1; qb = -1;
-    if (r.score < minsc || r.qe < 0) return;
-    for (int x = lane; x <= r.qe; x += 64) E.rq2[x] = q[r.qe - x];
-    wave_sync();
-    const SwRes rr = ksw_pass_any(E.rq2, r.qe + 1, target, tlen, r.te, P, p, r.score, lane);
-    wave_sync();
-    if (r.score == rr.score) { tb = r.te - rr.te; qb = r.qe - rr.qe; }
-}
-
-// mem_matesw's window of direction r for the mate region a (the rescued read l_ms long): [rb, re)
-// clipped to one contig (rid); true when bwa runs its SW there
+// mem_matesw's window of direction r for the mate region a: clipped to one contig (bns_fetch_seq)
 __device__ __forceinline__ bool g_mate_window(const DevGenome &G, const af_params &p, const S2Pes &pe, int r,
                                               const GReg &a, int l_ms, int64_t &rb, int64_t &re, int &rid) {
-    const int64_t l_pac = G.l_pac;
-    const bool is_rev = (r >> 1) != (r & 1);
-    const bool is_larger = !(r >> 1);
-    if (!is_rev) {
-        rb = is_larger ? a.rb + pe.low : a.rb - pe.high;
-        re = (is_larger ? a.rb + pe.high : a.rb - pe.low) + l_ms;
-    } else {
-        rb = (is_larger ? a.rb + pe.low : a.rb - pe.high) - l_ms;
-        re = is_larger ? a.rb + pe.high : a.rb - pe.low;
-    }
-    if (rb < 0) rb = 0;
-    if (re > l_pac << 1) re = l_pac << 1;
-    if (rb < re) g_fetch_clip(G, &rb, (rb + re) >> 1, &re, &rid);
-    // (rb >= re leaves rid from the previous direction, as bwa does; re - rb < min_seed_len then)
-    return a.rid == rid && re - rb >= p.min_seed_len;
+    return mate_window(G.l_pac, p, pe, r, a.rb, a.rid, l_ms, rb, re, rid,
+                       [&G](int64_t &b, int64_t &e, int &id) { g_fetch_clip(G, &b, (b + e) >> 1, &e, &id); });
 }
 
-// that window's ksw_align2 for the rescued read's codes qc (strand of direction r)
+// that window's ksw_align2 for the rescued read's codes qc, in the pair's LDS
 __device__ __forceinline__ void g_mate_ksw(const DevGenome &G, const af_params &p, const uint8_t *qc, int l_ms, int r,
                                            int64_t rb, int64_t re, int &sc, int &te, int &qe, int &tb, int &qb,
                                            int lane) {
     GPeLds &E = g_gpe;
-    const bool is_rev = (r >> 1) != (r & 1);
-    for (int x = lane; x < l_ms; x += 64) {
-        const int c = qc[is_rev ? l_ms - 1 - x : x];
-        E.rq[x] = (uint8_t)(is_rev ? (c < 4 ? 3 - c : 4) : c);
-    }
-    const bool staged = re - rb <= (int64_t)sizeof(E.tw);
-    if (staged)
-        for (int x = lane; x < (int)(re - rb); x += 64) E.tw[x] = G.T[rb + x];
-    wave_sync();
-    const int P = l_ms * p.a < 250 ? 16 : 8;
-    g_ksw_align2(E.rq, l_ms, staged ? E.tw : G.T + rb, (int)(re - rb), P, p.min_seed_len * p.a, p, sc, te, qe, tb, qb,
-                 lane);
+    mate_ksw(G.T, p, qc, l_ms, r, rb, re, E.rq, E.tw, E.rq2, sc, te, qe, tb, qb, lane);
 }
 
 // mem_matesw (oracle mem_matesw): rescue read mi (regions ma[0, *na)) in the insert-size window
@@ -2343,7 +2146,7 @@ __device__ bool g_matesw(const DevGenome &G, const af_params &p, const GOpt &o, 
         const int na0 = E.na[mi];
         for (int i = lane; i < na0; i += 64) {
             int64_t dist;
-            const int r = g_infer_dir(l_pac, a.rb, ma[i].rb, &dist);
+            const int r = infer_dir(l_pac, a.rb, ma[i].rb, &dist);
             if (dist >= E.pes[r].low && dist <= E.pes[r].high) bits |= 1 << r;
         }
         for (int r = 0; r < 4; ++r)
@@ -2357,7 +2160,7 @@ __device__ bool g_matesw(const DevGenome &G, const af_params &p, const GOpt &o, 
     bool deduped = false, dirty = false;
     for (int r = 0; r < 4; ++r) {
         if (skip[r]) continue;
-        const bool is_rev = (r >> 1) != (r & 1);
+        const bool is_rev = mate_is_rev(r);
         int64_t rb, re;
         if (g_mate_window(G, p, E.pes[r], r, a, l_ms, rb, re, rid)) {
             int sc, te, qe, tb, qb;
@@ -2392,10 +2195,7 @@ __device__ bool g_matesw(const DevGenome &G, const af_params &p, const GOpt &o, 
                 if (lane == 0) {
                     GReg b{};
                     b.rid = a.rid;
-                    b.qb = is_rev ? l_ms - (qe + 1) : qb;
-                    b.qe = is_rev ? l_ms - qb : qe + 1;
-                    b.rb = is_rev ? (l_pac << 1) - (rb + te + 1) : rb + tb;
-                    b.re = is_rev ? (l_pac << 1) - (rb + tb) : rb + te + 1;
+                    mate_region_span(b, l_pac, is_rev, rb, l_ms, te, qe, tb, qb);
                     b.score = sc;
                     b.secondary = -1;
                     b.seedcov = (int)((b.re - b.rb < b.qe - b.qb ? b.re - b.rb : b.qe - b.qb) >> 1);
@@ -2421,59 +2221,21 @@ __device__ bool g_matesw(const DevGenome &G, const af_params &p, const GOpt &o, 
     return true;
 }
 
-struct P64g { uint64_t x, y; };
-static_assert(sizeof(G2Box) * G2_BOXES >= sizeof(P64g) * AF_G_MAX_REG, "the boxes hold mem_pair's keys");
-struct GLtP64 {
-    __device__ bool operator()(const P64g &a, const P64g &b) const { return a.x < b.x || (a.x == b.x && a.y < b.y); }
-};
+static_assert(sizeof(G2Box) * G2_BOXES >= sizeof(P64) * AF_G_MAX_REG, "the boxes hold mem_pair's keys");
+// mem_pair's key of region i of read r: contigs in order, then the strand-folded offset in the contig
+__device__ __forceinline__ P64 g_pair_key(const DevGenome &G, const GReg &e, int i, int r) {
+    const int64_t l_pac = G.l_pac;
+    const int64_t x = e.rb < l_pac ? e.rb : (l_pac << 1) - 1 - e.rb;
+    return mem_pair_key((uint64_t)e.rid << 32 | (uint64_t)(x - G.ctg_off_d[e.rid]), e.score, i, e.rb >= l_pac, r);
+}
 
 // mem_pair (oracle mem_pair), lane 0: the best pair's score (0 if none) and z[]
 __device__ int g_mem_pair(const DevGenome &G, const af_params &p, const S2Pes *pes, GReg *a0, int n0, GReg *a1, int n1,
-                          int id, int z[2], P64g *v) {
-    const int64_t l_pac = G.l_pac;
+                          int id, int z[2], P64 *v) {
     int nv = 0;
-    GReg *aa[2] = {a0, a1};
-    const int nn[2] = {n0, n1};
-    for (int r = 0; r < 2; ++r)
-        for (int i = 0; i < nn[r]; ++i) {
-            const GReg &e = aa[r][i];
-            P64g key;
-            const int64_t x = e.rb < l_pac ? e.rb : (l_pac << 1) - 1 - e.rb;
-            key.x = (uint64_t)e.rid << 32 | (uint64_t)(x - G.ctg_off_d[e.rid]);
-            key.y = (uint64_t)(uint32_t)e.score << 32 | (uint64_t)i << 2 | (uint64_t)(e.rb >= l_pac) << 1 | (uint64_t)r;
-            v[nv++] = key;
-        }
-    ks_introsort(v, nv, GLtP64());
-    int y[4] = {-1, -1, -1, -1};
-    bool have = false;
-    P64g best{0, 0};
-    for (int i = 0; i < nv; ++i) {
-        for (int r = 0; r < 2; ++r) {
-            const int dir = r << 1 | (int)(v[i].y >> 1 & 1);
-            if (pes[dir].failed) continue;
-            const int which = r << 1 | (int)((v[i].y & 1) ^ 1);
-            if (y[which] < 0) continue;
-            for (int k = y[which]; k >= 0; --k) {
-                if ((int)(v[k].y & 3) != which) continue;
-                const int64_t dist = (int64_t)v[i].x - (int64_t)v[k].x;
-                if (dist > pes[dir].high) break;
-                if (dist < pes[dir].low) continue;
-                const double ns = ((double)dist - pes[dir].avg) / pes[dir].std;
-                int q = (int)((double)((v[i].y >> 32) + (v[k].y >> 32)) + .721 * log(2. * erfc(fabs(ns) * 0.70710678118654752440)) * p.a + .499);
-                if (q < 0) q = 0;
-                P64g u;
-                u.y = (uint64_t)k << 32 | (uint64_t)i;
-                u.x = (uint64_t)q << 32 | (hash_64(u.y ^ (uint64_t)(int64_t)(int32_t)((uint32_t)id << 8)) & 0xffffffffU);
-                if (!have || GLtP64()(best, u)) { best = u; have = true; }
-            }
-        }
-        y[v[i].y & 3] = i;
-    }
-    if (!have) return 0;
-    const int i = (int)(best.y >> 32), k = (int)(best.y << 32 >> 32);
-    z[v[i].y & 1] = (int)(v[i].y << 32 >> 34);
-    z[v[k].y & 1] = (int)(v[k].y << 32 >> 34);
-    return (int)(best.x >> 32);
+    for (int i = 0; i < n0; ++i) v[nv++] = g_pair_key(G, a0[i], i, 0);
+    for (int i = 0; i < n1; ++i) v[nv++] = g_pair_key(G, a1[i], i, 1);
+    return mem_pair_scan(v, nv, pes, p, id, z);
 }
 
 // mem_pair on the wave for long region lists (the same result as g_mem_pair: its keys are unique,
@@ -2483,30 +2245,24 @@ __device__ int g_mem_pair(const DevGenome &G, const af_params &p, const S2Pes *p
 // down, stopping at the first (highest) k past the insert-size window as bwa's break does.  Every
 // lane returns the score (0: none) and z.
 __device__ int g_mem_pair_w(const DevGenome &G, const af_params &p, const S2Pes *pes, const GReg *a0, int n0,
-                            const GReg *a1, int n1, int id, int z[2], P64g *v, P64g *tmp, int lane) {
-    const int64_t l_pac = G.l_pac;
+                            const GReg *a1, int n1, int id, int z[2], P64 *v, P64 *tmp, int lane) {
     const int nv = n0 + n1;
     for (int t = lane; t < nv; t += 64) {
         const int r = t >= n0, i = t - (r ? n0 : 0);
-        const GReg &e = r ? a1[i] : a0[i];
-        const int64_t x = e.rb < l_pac ? e.rb : (l_pac << 1) - 1 - e.rb;
-        P64g key;
-        key.x = (uint64_t)e.rid << 32 | (uint64_t)(x - G.ctg_off_d[e.rid]);
-        key.y = (uint64_t)(uint32_t)e.score << 32 | (uint64_t)i << 2 | (uint64_t)(e.rb >= l_pac) << 1 | (uint64_t)r;
-        v[t] = key;
+        v[t] = g_pair_key(G, r ? a1[i] : a0[i], i, r);
     }
     __threadfence_block();
     wave_sync();
-    if (!wave_rank_sort(v, nv, GLtP64(), tmp, lane)) {  // (keys name their entry: never taken)
-        if (lane == 0) ks_introsort(v, nv, GLtP64());
+    if (!wave_rank_sort(v, nv, LtP64(), tmp, lane)) {  // (keys name their entry: never taken)
+        if (lane == 0) ks_introsort(v, nv, LtP64());
         __threadfence_block();
         wave_sync();
     }
     int y[4] = {-1, -1, -1, -1};
     bool have = false;
-    P64g best{0, 0};
+    P64 best{0, 0};
     for (int i = 0; i < nv; ++i) {
-        const P64g vi = v[i];
+        const P64 vi = v[i];
         for (int r = 0; r < 2; ++r) {
             const int dir = r << 1 | (int)(vi.y >> 1 & 1);
             if (pes[dir].failed) continue;
@@ -2517,7 +2273,7 @@ __device__ int g_mem_pair_w(const DevGenome &G, const af_params &p, const S2Pes 
                 const int k = k0 - lane;
                 bool valid = false, brk = false;
                 int64_t dist = 0;
-                P64g vk{0, 0};
+                P64 vk{0, 0};
                 if (k >= 0) {
                     vk = v[k];
                     valid = (int)(vk.y & 3) == which;
@@ -2527,13 +2283,8 @@ __device__ int g_mem_pair_w(const DevGenome &G, const af_params &p, const S2Pes 
                 const uint64_t bm = __ballot(brk);
                 const int first = bm ? (int)__builtin_ctzll(bm) : 64;  // lanes below it precede bwa's break
                 if (valid && lane < first && dist >= lo) {
-                    const double ns = ((double)dist - pes[dir].avg) / pes[dir].std;
-                    int q = (int)((double)((vi.y >> 32) + (vk.y >> 32)) + .721 * log(2. * erfc(fabs(ns) * 0.70710678118654752440)) * p.a + .499);
-                    if (q < 0) q = 0;
-                    P64g u;
-                    u.y = (uint64_t)k << 32 | (uint64_t)i;
-                    u.x = (uint64_t)q << 32 | (hash_64(u.y ^ (uint64_t)(int64_t)(int32_t)((uint32_t)id << 8)) & 0xffffffffU);
-                    if (!have || GLtP64()(best, u)) { best = u; have = true; }
+                    const P64 u = mem_pair_score(vi, vk, i, k, dist, pes[dir], p, id);
+                    if (!have || LtP64()(best, u)) { best = u; have = true; }
                 }
                 if (bm) break;
             }
@@ -2541,28 +2292,23 @@ __device__ int g_mem_pair_w(const DevGenome &G, const af_params &p, const S2Pes 
         y[vi.y & 3] = i;
     }
     // the lanes' best to lane 0 through tmp (its sort copy is dead)
-    tmp[lane] = have ? best : P64g{0, 0};
+    tmp[lane] = have ? best : P64{0, 0};
     reinterpret_cast<uint8_t *>(tmp + 64)[lane] = have ? 1 : 0;
     __threadfence_block();
     wave_sync();
     int res = 0;
     if (lane == 0) {
         bool any = false;
-        P64g b{0, 0};
+        P64 b{0, 0};
         for (int l = 0; l < 64; ++l)
-            if (reinterpret_cast<const uint8_t *>(tmp + 64)[l] && (!any || GLtP64()(b, tmp[l]))) { b = tmp[l]; any = true; }
-        if (any) {
-            const int i = (int)(b.y >> 32), k = (int)(b.y << 32 >> 32);
-            z[v[i].y & 1] = (int)(v[i].y << 32 >> 34);
-            z[v[k].y & 1] = (int)(v[k].y << 32 >> 34);
-            res = (int)(b.x >> 32);
-        }
+            if (reinterpret_cast<const uint8_t *>(tmp + 64)[l] && (!any || LtP64()(b, tmp[l]))) { b = tmp[l]; any = true; }
+        if (any) res = mem_pair_pick(v, b, z);
         tmp[0].x = (uint64_t)(uint32_t)res | (uint64_t)(uint32_t)z[0] << 32;
         tmp[0].y = (uint64_t)(uint32_t)z[1];
     }
     __threadfence_block();
     wave_sync();
-    const P64g o = tmp[0];
+    const P64 o = tmp[0];
     z[0] = (int)(o.x >> 32); z[1] = (int)(uint32_t)o.y;
     res = (int)(uint32_t)o.x;
     wave_sync();
@@ -2588,10 +2334,10 @@ __global__ __launch_bounds__(64, 2) void k_g_pe(DevGenome G, const uint8_t *__re
     // region lists of both ends (and the rescue copies) in the wave's scratch
     GReg *A[2] = {S.reg, reinterpret_cast<GReg *>(S.pool)};
     GReg *B = reinterpret_cast<GReg *>(S.ch);
-    P64g *V = reinterpret_cast<P64g *>(S.seed);
+    P64 *V = reinterpret_cast<P64 *>(S.seed);
     static_assert((size_t)AF_G_MAX_OCC * sizeof(GSeed) >= (size_t)(AF_G_MAX_REG + 1) * sizeof(GReg), "pool holds a region list");
     static_assert((size_t)AF_G_MAX_CHAIN * sizeof(GChain) >= 2 * (size_t)(AF_G_MAX_REG + 1) * sizeof(GReg), "ch holds 2 lists");
-    static_assert((size_t)AF_G_MAX_OCC * sizeof(GSeed) >= 2 * (size_t)(AF_G_MAX_REG + 4) * sizeof(P64g), "seed holds v");
+    static_assert((size_t)AF_G_MAX_OCC * sizeof(GSeed) >= 2 * (size_t)(AF_G_MAX_REG + 4) * sizeof(P64), "seed holds v");
     // mode 0: every pair; 1: every pair, those with at least w.pe.min_windows rescue windows left
     // to k_g_pe_jobs (their SWs) and mode 2 (the rest, with those SWs' results)
     const GPeSpec &X = w.pe;
@@ -2630,7 +2376,7 @@ __global__ __launch_bounds__(64, 2) void k_g_pe(DevGenome G, const uint8_t *__re
             for (int k = lane; k < na; k += 64) A[m][k] = w.reg[w.reg_off[r] + k];
             if (lane == 0) { E.len[m] = l; E.na[m] = na; E.ovf[m] = nr < 0; }
         }
-        if (lane < 4) E.pes[lane] = sw.pes[(int64_t)g_chunk_of(sw, pp) * 4 + lane];
+        if (lane < 4) E.pes[lane] = sw.pes[(int64_t)chunk_of(sw, pp) * 4 + lane];
         wave_sync();
         // mate rescue for the top hits of each end (copies taken before any rescue)
         if (lane == 0) {
@@ -2697,13 +2443,13 @@ __global__ __launch_bounds__(64, 2) void k_g_pe(DevGenome G, const uint8_t *__re
         const bool pair_w = E.na[0] && E.na[1] && npr >= G_RANK_MIN && npr <= AF_G_MAX_REG;
         if (pair_w)
             o_sc_w = g_mem_pair_w(G, p, E.pes, A[0], E.na[0], A[1], E.na[1], (int)(uint32_t)(o.pair_base + pp), zw,
-                                  reinterpret_cast<P64g *>(g_box), V, lane);
+                                  reinterpret_cast<P64 *>(g_box), V, lane);
         if (lane == 0) {
             const uint64_t id = (uint64_t)(o.pair_base + pp);
             int z[2] = {zw[0], zw[1]}, extra = 1, mode = 0;  // mode 1: paired records
             int o_sc = 0;
             // mem_pair's sort keys in LDS (the boxes' space) when they fit
-            P64g *Vp = E.na[0] + E.na[1] <= AF_G_MAX_REG ? reinterpret_cast<P64g *>(g_box) : V;
+            P64 *Vp = E.na[0] + E.na[1] <= AF_G_MAX_REG ? reinterpret_cast<P64 *>(g_box) : V;
             if (E.na[0] && E.na[1] &&
                 (o_sc = pair_w ? o_sc_w : g_mem_pair(G, p, E.pes, A[0], E.na[0], A[1], E.na[1], (int)(uint32_t)id, z, Vp)) > 0) {
                 int is_multi = 0;
@@ -2761,7 +2507,7 @@ __global__ __launch_bounds__(64, 2) void k_g_pe(DevGenome G, const uint8_t *__re
         } else {
             if (H.mate[0].rid == H.mate[1].rid && H.mate[0].rid >= 0) {
                 int64_t dist;
-                const int d = g_infer_dir(G.l_pac, A[0][0].rb, A[1][0].rb, &dist);
+                const int d = infer_dir(G.l_pac, A[0][0].rb, A[1][0].rb, &dist);
                 if (!E.pes[d].failed && dist >= E.pes[d].low && dist <= E.pes[d].high) extra |= 2;
             }
             for (int i = 0; i < 2; ++i) {
@@ -2822,7 +2568,7 @@ __global__ __launch_bounds__(64, 2) void k_g_pe_jobs(DevGenome G, const uint8_t 
         const int64_t rm = 2 * pp + !i;
         const int l_ms = read_len(lens, rm, stride);
         for (int x = lane; x < l_ms; x += 64) E.q[0][x] = nt4(reads[rm * (int64_t)stride + x]);
-        if (lane < 4) E.pes[lane] = sw.pes[(int64_t)g_chunk_of(sw, pp) * 4 + lane];
+        if (lane < 4) E.pes[lane] = sw.pes[(int64_t)chunk_of(sw, pp) * 4 + lane];
         // bj: end i's j-th region scoring within pen_unpaired of its best (k_g_pe's copy list)
         const GReg *ai = w.reg + w.reg_off[2 * pp + i];
         const int na = w.reg_n[2 * pp + i] > 0 ? w.reg_n[2 * pp + i] : 0;
@@ -2912,6 +2658,55 @@ extern "C" int af_debug_wave_introsort(const uint64_t *keys, int32_t n, uint64_t
     return rc;
 }
 
+// ---- test hook: the shared kbtree (bwa_mem_dev.h kb_*) on either store, lane 0 of one wave.  Chains
+// 0..n-1 with keys pos[] are inserted in turn: lower[i] = kb_lower(pos[i]) before chain i goes in (-1
+// on the empty tree), order[] = the final in-order traversal.  store 0: the S2 store (s2.hip; n <=
+// AF_S2_MAX_CHAIN, 32-bit keys); store 1: the genome store with g_mem_chain's LDS / scratch split
+// (n <= AF_G_MAX_CHAIN).  tests/test_gpu_genome.py::test_kbtree_equals_klib.
+__global__ __launch_bounds__(64) void k_debug_kbtree_g(const int64_t *__restrict__ pos, int n, GChain *__restrict__ ch,
+                                                       GKb *__restrict__ kb, int32_t *__restrict__ lower,
+                                                       int32_t *__restrict__ order, int32_t *__restrict__ count) {
+    if (threadIdx.x != 0) return;
+    GChainLds &C = *reinterpret_cast<GChainLds *>(g_box);
+    for (int i = 0; i < n; ++i) {
+        ch[i].pos = pos[i];
+        if (i < G_POS_LDS) C.pos[i] = pos[i];
+    }
+    GTree tree{C.node, kb, 0, 0, ch, C.pos};
+    *count = kb_debug_fill(tree, n, lower, order);
+}
+extern "C" int af_debug_kbtree(const int64_t *pos, int32_t n, int32_t store, int32_t *lower, int32_t *order) {
+    if (n < 1 || !pos || !lower || !order || store < 0 || store > 1) return -1;
+    if (n > (store ? AF_G_MAX_CHAIN : AF_S2_MAX_CHAIN)) return -1;
+    if (!store)
+        for (int i = 0; i < n; ++i)
+            if (pos[i] != (int64_t)(int32_t)pos[i]) return -1;
+    int64_t *dp = nullptr;
+    int32_t *dl = nullptr;  // lower[n], order[n], count
+    GChain *dc = nullptr;
+    GKb *dk = nullptr;
+    int32_t count = -1;
+    int rc = -1;
+    if (hipMalloc(&dp, sizeof(int64_t) * (size_t)n) == hipSuccess &&
+        hipMalloc(&dl, sizeof(int32_t) * (2 * (size_t)n + 1)) == hipSuccess &&
+        hipMalloc(&dc, sizeof(GChain) * (size_t)n) == hipSuccess &&
+        hipMalloc(&dk, sizeof(GKb) * (size_t)G_KB_NODES) == hipSuccess &&
+        hipMemcpy(dp, pos, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess) {
+        hipError_t e = hipSuccess;
+        if (store) {
+            hipLaunchKernelGGL(k_debug_kbtree_g, dim3(1), dim3(64), 0, 0, dp, n, dc, dk, dl, dl + n, dl + 2 * n);
+            e = hipGetLastError();
+        } else e = af_launch_debug_kbtree_s2(dp, n, dl, dl + n, dl + 2 * n);
+        if (e == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+            hipMemcpy(lower, dl, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(order, dl + n, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(&count, dl + 2 * n, sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess && count == n)
+            rc = 0;
+    }
+    (void)hipFree(dp); (void)hipFree(dl); (void)hipFree(dc); (void)hipFree(dk);
+    return rc;
+}
+
 #ifdef AF_G_PROF
 static int32_t *h_gprof = nullptr;
 static int64_t h_gprof_cap = 0;
@@ -2950,15 +2745,6 @@ hipError_t af_launch_genome_regions(const DevGenome &G, const uint8_t *reads, in
                                     uint8_t *g1_scratch, int n_g1_threads, uint8_t *g2_scratch, int n_g2_waves,
                                     uint8_t *zscratch, hipStream_t s) {
     GPROF(gprof_next(s);)
-    {
-        static int chain_arr = G_ARR;  // the value the symbol holds (read by the kernel at its launch)
-        const char *e = getenv("AF_G_CHAIN_ARR");
-        const int want = e ? std::max(0, std::min(G_ARR, atoi(e))) : G_ARR;
-        if (want != chain_arr) {
-            chain_arr = want;
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_chain_arr), &chain_arr, sizeof(int));
-        }
-    }
     hipLaunchKernelGGL(k_g_zero, dim3(1), dim3(64), 0, s, w, cap, w.heads);
     // one lane per read, at most the scratch's lanes (idle lanes refill from w.g1_next)
     const int64_t g1_waves = std::max<int64_t>(1, std::min<int64_t>(n_g1_threads / 64, (cap + 63) / 64));

@@ -20,7 +20,7 @@
 // Serial parts of bwa (kbtree, klib introsort, the chain and pair loops) run on lane 0 over
 // per-wave LDS state; the DP and the list scans run on the whole wave.  Double-precision
 // arithmetic (pestat, patching, pair scores) is kept unfused so it rounds as the C oracle does.
-#include "bwa_dev.h"
+#include "bwa_mem_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -34,8 +34,8 @@ struct S2Pm { int16_t s, t; int32_t r; };          // a MEM: query [s, t), text 
 struct S2Si { int16_t qb, qe, cnt, occ0; };        // a seed interval and its occurrences
 struct S2Seed { int32_t rbeg; int16_t qbeg, len; };  // mem_seed_t (score = len)
 struct S2Chain { int16_t n, first, kept, seed0; int32_t w, pos; };  // mem_chain_t
-constexpr int KB_T = 5, KB_MAXK = 2 * KB_T - 1, KB_NODES = 2 * AF_S2_MAX_CHAIN + 4;
-struct S2Kb { uint8_t n, internal, key[KB_MAXK], ptr[KB_MAXK + 1]; };
+constexpr int KB_NODES = 2 * AF_S2_MAX_CHAIN + 4;
+typedef KbNode<uint8_t> S2Kb;
 
 struct __attribute__((aligned(16))) S2Lds {
     union {
@@ -405,126 +405,27 @@ __device__ void s2_collect_intv(const DevText &X, const af_params &p, const S2Op
 }
 
 // =========================================================================== K2: chains
-// klib kbtree (t = 5) over chain indices keyed by chain pos; lane 0 only (oracle kb_*)
-__device__ __forceinline__ int kb_cmp(int x, int32_t kpos) {
-    const int32_t a = g_s2.ch[x].pos;
-    return (kpos < a) - (a < kpos);
-}
-__device__ int kb_getp_aux(const S2Kb &x, int32_t kpos, int *r) {
-    int tr, *rr, begin = 0, end = x.n;
-    if (x.n == 0) return -1;
-    rr = r ? r : &tr;
-    while (begin < end) {
-        const int mid = (begin + end) >> 1;
-        if (kb_cmp(x.key[mid], kpos) < 0) begin = mid + 1;
-        else end = mid;
-    }
-    if (begin == x.n) { *rr = 1; return x.n - 1; }
-    if ((*rr = -kb_cmp(x.key[begin], kpos)) < 0) --begin;
-    return begin;
-}
-__device__ int kb_new(int internal) {
-    S2Lds &S = g_s2;
-    const int zi = S.cnt[6]++;
-    S2Kb &z = S.x.kb[zi];
-    z.n = 0; z.internal = (uint8_t)internal;
-    return zi;
-}
-__device__ int kb_lower(int32_t kpos) {
-    S2Lds &S = g_s2;
-    int r = 0, lower = -1, xi = S.cnt[5];
-    while (xi >= 0) {
-        const S2Kb &x = S.x.kb[xi];
-        const int i = kb_getp_aux(x, kpos, &r);
-        if (i >= 0 && r == 0) return x.key[i];
-        if (i >= 0) lower = x.key[i];
-        if (!x.internal) return lower;
-        xi = x.ptr[i + 1];
-    }
-    return lower;
-}
-__device__ void kb_split(int xi, int i, int yi) {
-    S2Lds &S = g_s2;
-    const int zi = kb_new(S.x.kb[yi].internal);
-    S2Kb &x = S.x.kb[xi], &y = S.x.kb[yi], &z = S.x.kb[zi];
-    z.n = KB_T - 1;
-    for (int u = 0; u < KB_T - 1; ++u) z.key[u] = y.key[KB_T + u];
-    if (y.internal)
-        for (int u = 0; u < KB_T; ++u) z.ptr[u] = y.ptr[KB_T + u];
-    y.n = KB_T - 1;
-    for (int u = x.n; u >= i + 1; --u) x.ptr[u + 1] = x.ptr[u];
-    x.ptr[i + 1] = (uint8_t)zi;
-    for (int u = x.n - 1; u >= i; --u) x.key[u + 1] = x.key[u];
-    x.key[i] = y.key[KB_T - 1];
-    ++x.n;
-}
-__device__ void kb_putp(int k) {
-    S2Lds &S = g_s2;
-    const int32_t kpos = S.ch[k].pos;
-    int xi = S.cnt[5];
-    if (S.x.kb[xi].n == KB_MAXK) {
-        const int si = kb_new(1);
-        S.x.kb[si].ptr[0] = (uint8_t)xi;
-        S.cnt[5] = si;
-        kb_split(si, 0, xi);
-        xi = si;
-    }
-    for (;;) {  // __kb_putp_aux, iteratively
-        S2Kb &x = S.x.kb[xi];
-        if (!x.internal) {
-            const int i = kb_getp_aux(x, kpos, nullptr);
-            for (int u = x.n - 1; u >= i + 1; --u) x.key[u + 1] = x.key[u];
-            x.key[i + 1] = (uint8_t)k;
-            ++x.n;
-            return;
-        }
-        int i = kb_getp_aux(x, kpos, nullptr) + 1;
-        if (S.x.kb[x.ptr[i]].n == KB_MAXK) {
-            kb_split(xi, i, x.ptr[i]);
-            if (kb_cmp(S.x.kb[xi].key[i], kpos) < 0) ++i;  // klib: cmp(*k, key[i]) > 0, k past the promoted key
-        }
-        xi = S.x.kb[xi].ptr[i];
-    }
-}
-__device__ int kb_traverse() {
-    S2Lds &S = g_s2;
-    int stk_node[8], stk_i[8], top = 0, n = 0;
-    stk_node[0] = S.cnt[5]; stk_i[0] = 0;
-    // in-order: for a node, child[i] then key[i] for i < n, then child[n]
-    if (!S.x.kb[stk_node[0]].internal) {
-        const S2Kb &x = S.x.kb[stk_node[0]];
-        for (int i = 0; i < x.n; ++i) S.order[n++] = x.key[i];
-        return n;
-    }
-    top = 1;
-    while (top > 0) {
-        const int xi = stk_node[top - 1];
-        const int i = stk_i[top - 1];
-        const S2Kb &x = S.x.kb[xi];
-        if (!x.internal) {
-            for (int u = 0; u < x.n; ++u) S.order[n++] = x.key[u];
-            --top;
-            continue;
-        }
-        if (i > x.n) { --top; continue; }
-        stk_i[top - 1] = i + 1;
-        if (i > 0) S.order[n++] = x.key[i - 1];
-        stk_node[top] = x.ptr[i]; stk_i[top] = 0; ++top;
-    }
-    return n;
-}
+// the kbtree's store (bwa_mem_dev.h kb_*): nodes, chain keys, root and node count in the wave's LDS.
+// At most AF_S2_MAX_CHAIN keys, so KB_NODES nodes never run out.
+struct S2Tree {
+    typedef uint8_t Idx;
+    typedef int32_t Pos;
+    static constexpr int DEPTH = 8;
+    __device__ S2Kb &nd(int i) const { return g_s2.x.kb[i]; }
+    __device__ int32_t pos(int x) const { return g_s2.ch[x].pos; }
+    __device__ int root() const { return g_s2.cnt[5]; }
+    __device__ void set_root(int i) const { g_s2.cnt[5] = i; }
+    __device__ int alloc() const { return g_s2.cnt[6]++; }
+    __device__ bool full() const { return false; }
+};
 
 // test_and_merge (lane 0; oracle test_and_merge)
 __device__ int s2_test_and_merge(int ci, const S2Seed &p, int64_t l_pac, int w, int max_chain_gap) {
     S2Lds &S = g_s2;
     S2Chain &c = S.ch[ci];
-    const S2Seed first = S.pool[c.seed0], last = S.pool[S.last_of[ci]];
-    const int64_t qend = (int64_t)last.qbeg + last.len, rend = (int64_t)last.rbeg + last.len;
-    if (p.qbeg >= first.qbeg && p.qbeg + p.len <= qend && p.rbeg >= first.rbeg && (int64_t)p.rbeg + p.len <= rend)
-        return 1;
-    if ((last.rbeg < l_pac || first.rbeg < l_pac) && p.rbeg >= l_pac) return 0;
-    const int64_t x = p.qbeg - last.qbeg, y = (int64_t)p.rbeg - last.rbeg;
-    if (y >= 0 && x - y <= w && y - x <= w && x - last.len < max_chain_gap && y - last.len < max_chain_gap) {
+    const int m = chain_merge_test(S.pool[c.seed0], S.pool[S.last_of[ci]], p, l_pac, w, max_chain_gap);
+    if (m == MERGE_CONTAINED) return 1;
+    if (m == MERGE_APPEND) {
         if (S.cnt[2] >= AF_S2_MAX_OCC) return -1;
         const int k = S.cnt[2]++;
         S.pool[k] = p;
@@ -548,9 +449,9 @@ __device__ int s2_mem_chain(const DevText &X, const af_params &p, const S2Opt &o
     (void)nocc_used;
     S.cnt[2] = 0;
     S.cnt[4] = 0;
-    S.cnt[5] = -1;
     S.cnt[6] = 0;
-    S.cnt[5] = kb_new(0);
+    S2Tree tree;
+    tree.set_root(kb_new(tree, 0));
     for (int i = 0; i < nsi; ++i) {
         const S2Si v = S.y.a.si[i];
         const int slen = v.qe - v.qb;
@@ -563,7 +464,7 @@ __device__ int s2_mem_chain(const DevText &X, const af_params &p, const S2Opt &o
             if (s.rbeg < l_pac && (int64_t)s.rbeg + s.len > l_pac) continue;  // bns_intv2rid < 0
             bool to_add = false;
             if (S.cnt[4]) {
-                const int lower = kb_lower(s.rbeg);
+                const int lower = kb_lower(tree, s.rbeg);
                 if (lower < 0) to_add = true;
                 else {
                     const int r = s2_test_and_merge(lower, s, l_pac, p.w, o.max_chain_gap);
@@ -579,12 +480,12 @@ __device__ int s2_mem_chain(const DevText &X, const af_params &p, const S2Opt &o
                 const int nc = S.cnt[4];
                 S.ch[nc] = S2Chain{1, -1, 0, (int16_t)kk, 0, s.rbeg};
                 S.last_of[nc] = (int16_t)kk;
-                kb_putp(nc);
+                kb_putp(tree, nc);
                 S.cnt[4] = nc + 1;
             }
         }
     }
-    const int no = kb_traverse();
+    const int no = kb_traverse(tree, S.order);
     // reorder the chains (tree order) and compact their seeds
     for (int a = 0; a < no; ++a) S.x.chtmp[a] = S.ch[S.order[a]];
     int ns = 0;
@@ -598,27 +499,6 @@ __device__ int s2_mem_chain(const DevText &X, const af_params &p, const S2Opt &o
     return no;
 }
 
-__device__ int s2_chain_weight(const S2Chain &c) {
-    const S2Seed *sd = g_s2.y.c.seed + c.seed0;
-    int64_t end = 0;
-    int w = 0, tmp;
-    for (int j = 0; j < c.n; ++j) {
-        const S2Seed s = sd[j];
-        if (s.qbeg >= end) w += s.len;
-        else if (s.qbeg + s.len > end) w += (int)(s.qbeg + s.len - end);
-        end = end > s.qbeg + s.len ? end : s.qbeg + s.len;
-    }
-    tmp = w; w = 0; end = 0;
-    for (int j = 0; j < c.n; ++j) {
-        const S2Seed s = sd[j];
-        if (s.rbeg >= end) w += s.len;
-        else if ((int64_t)s.rbeg + s.len > end) w += (int)((int64_t)s.rbeg + s.len - end);
-        end = end > (int64_t)s.rbeg + s.len ? end : (int64_t)s.rbeg + s.len;
-    }
-    w = w < tmp ? w : tmp;
-    return w < 1 << 30 ? w : (1 << 30) - 1;
-}
-
 struct LtFlt {
     __device__ bool operator()(const S2Chain &a, const S2Chain &b) const { return a.w > b.w; }
 };
@@ -628,7 +508,7 @@ __device__ int s2_chain_flt(int n_chn, const af_params &p, const S2Opt &o) {
     S2Lds &S = g_s2;
     S2Chain *a = S.ch;
     if (n_chn == 0) return 0;
-    for (int i = 0; i < n_chn; ++i) { a[i].first = -1; a[i].kept = 0; a[i].w = s2_chain_weight(a[i]); }
+    for (int i = 0; i < n_chn; ++i) { a[i].first = -1; a[i].kept = 0; a[i].w = chain_weight(S.y.c.seed + a[i].seed0, a[i].n); }
     ks_introsort(a, n_chn, LtFlt());
     auto beg = [&](const S2Chain &c) { return (int)S.y.c.seed[c.seed0].qbeg; };
     auto endq = [&](const S2Chain &c) {
@@ -1043,40 +923,6 @@ __global__ __launch_bounds__(64, AF_S2_WPS) void k_s2_regions(DevText X, const u
 }
 
 // ============================================================================ K3a
-__device__ __forceinline__ int s2_chunk_of(const S2Work &w, int64_t pp) {
-    if (w.ppc) return (int)(pp / w.ppc);
-    int lo = 0, hi = *w.n_chunks;  // cstart[lo] <= pp < cstart[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (w.cstart[mid] <= pp) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ int s2_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist) {
-    const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-    const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-    *dist = p2 > b1 ? p2 - b1 : b1 - p2;
-    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
-
-// cal_sub (oracle cal_sub) over a pool region list
-__device__ int s2_cal_sub(const S2Reg *a, int n, int msl, int asc) {
-    const S2Reg a0 = a[0];
-    int j;
-    for (j = 1; j < n; ++j) {
-        const S2Reg aj = a[j];
-        const int b_max = aj.qb > a0.qb ? aj.qb : a0.qb;
-        const int e_min = aj.qe < a0.qe ? aj.qe : a0.qe;
-        if (e_min > b_max) {
-            const int min_l = aj.qe - aj.qb < a0.qe - a0.qb ? aj.qe - aj.qb : a0.qe - a0.qb;
-            if ((float)(e_min - b_max) >= (float)min_l * 0.5f) break;
-        }
-    }
-    return j < n ? a[j].score : msl * asc;
-}
-
 // One workgroup per AF_S2_CLS_PAIRS consecutive pairs: the listed pairs are gathered in LDS and
 // appended with one atomic per workgroup; insert sizes go to the chunk histograms.
 constexpr int CLS_THREADS = 256, CLS_PER = 16, AF_S2_CLS_PAIRS = CLS_THREADS * CLS_PER;
@@ -1113,12 +959,12 @@ __global__ __launch_bounds__(CLS_THREADS) void k_s2_classify(int64_t n_pairs, in
         if (m0.y > 0 && m1.y > 0) {  // mem_pestat's candidate unique pairs
             const S2Reg *a0 = w.pool + m0.x, *a1 = w.pool + m1.x;
             const int s0 = a0[0].score, s1 = a1[0].score;
-            if (!((double)s2_cal_sub(a0, m0.y, p.min_seed_len, p.a) > 0.8 * s0) &&
-                !((double)s2_cal_sub(a1, m1.y, p.min_seed_len, p.a) > 0.8 * s1)) {
+            if (!((double)cal_sub(a0, m0.y, p.min_seed_len, p.a) > 0.8 * s0) &&
+                !((double)cal_sub(a1, m1.y, p.min_seed_len, p.a) > 0.8 * s1)) {
                 int64_t is;
-                const int dir = s2_infer_dir(l_pac, a0[0].rb, a1[0].rb, &is);
+                const int dir = infer_dir(l_pac, a0[0].rb, a1[0].rb, &is);
                 if (is && is <= o.max_ins) {
-                    const int c = s2_chunk_of(w, pp);
+                    const int c = chunk_of(w, pp);
                     atomicAdd(&w.ghist[((int64_t)c * 4 + dir) * (o.max_ins + 1) + is], 1);
                 }
             }
@@ -1215,8 +1061,6 @@ struct PeReg {
     uint64_t hash;
     int32_t secondary, pad;
 };
-struct P64 { uint64_t x, y; };
-constexpr int PE_TW = 2048;  // rescue windows up to this many bases are staged in LDS
 struct __attribute__((aligned(16))) PeLds {
     PeReg a[2][AF_S2_MAX_REG];
     int64_t brb[2][AF_S2_MAX_REG];
@@ -1238,20 +1082,6 @@ struct S2Plan {
     int32_t which[2], sec[2], extra, ovf;
 };
 
-// ksw_align2 with KSW_XSUBO | KSW_XSTART (oracle ksw_align2): score, te, qe and the start (tb, qb)
-__device__ void s2_ksw_align2(const uint8_t *q, int qlen, const uint8_t *target, int tlen, int P, int minsc,
-                              const af_params &p, int &score, int &te, int &qe, int &tb, int &qb, int lane) {
-    PeLds &E = g_pe;
-    const SwRes r = ksw_pass_any(q, qlen, target, tlen, -1, P, p, 0x10000, lane);
-    score = r.score; te = r.te; qe = r.qe; tb = -1; qb = -1;
-    if (r.score < minsc || r.qe < 0) return;
-    for (int x = lane; x <= r.qe; x += 64) E.rq2[x] = q[r.qe - x];
-    wave_sync();
-    const SwRes rr = ksw_pass_any(E.rq2, r.qe + 1, target, tlen, r.te, P, p, r.score, lane);
-    wave_sync();
-    if (r.score == rr.score) { tb = r.te - rr.te; qb = r.qe - rr.qe; }
-}
-
 // mem_sort_dedup_patch without patching (mate-SW context) on the wave.  The two sorts run over
 // keys (re | index; rb, score, qb | index): by rank on the wave when no two keys tie, else klib's
 // introsort on lane 0 -- its swaps depend only on the comparator's answers, so the order, ties
@@ -1262,15 +1092,8 @@ __device__ void s2_ksw_align2(const uint8_t *q, int qlen, const uint8_t *target,
 constexpr int PE_W8 = (int)(sizeof(PeReg) / 8);  // a region moves as this many 8-byte words
 static_assert(AF_S2_MAX_REG <= 32 && sizeof(PeReg) % 8 == 0 && sizeof(P64) * 2 * AF_S2_MAX_REG >= 32 * AF_S2_MAX_REG,
               "the dedup moves <= 32 regions through registers; its keys fit E.v");
-struct S2KeyRe {  // re << 6 | index
-    __device__ bool operator()(uint64_t a, uint64_t b) const { return (a >> 6) < (b >> 6); }
-};
-struct S2Key16 { int64_t x; int32_t y; int32_t z; };
-struct S2KeyArs {  // x = rb, y = score, z = qb << 8 | index: score desc, rb, qb (LtArs)
-    __device__ bool operator()(const S2Key16 &a, const S2Key16 &b) const {
-        return a.y > b.y || (a.y == b.y && (a.x < b.x || (a.x == b.x && (a.z >> 8) < (b.z >> 8))));
-    }
-};
+typedef KeyRe<6> S2KeyRe;    // re << 6 | index
+typedef KeyArs<8> S2KeyArs;  // z = qb << 8 | index
 // a[k] = old a[from(k)] for k < m <= 64 (wave; through registers)
 template <class F>
 __device__ __forceinline__ void s2_regs_gather(PeReg *a, int m, F from, int lane) {
@@ -1328,11 +1151,11 @@ __device__ int s2_dedup_nopatch(PeReg *a, int n, int max_chain_gap, int lane) {
     const bool live = lane < n && a[lane].r.qe > a[lane].r.qb;
     const uint64_t lm = __ballot(live);
     const int m = __popcll(lm);
-    S2Key16 *k2 = reinterpret_cast<S2Key16 *>(E.v), *t2 = k2 + AF_S2_MAX_REG;
+    Key16 *k2 = reinterpret_cast<Key16 *>(E.v), *t2 = k2 + AF_S2_MAX_REG;
     if (live) {
         const int pos = __popcll(lm & ((1ull << lane) - 1));
         const S2Reg &r = a[lane].r;
-        k2[pos] = S2Key16{r.rb, r.score, r.qb << 8 | lane};
+        k2[pos] = Key16{r.rb, r.score, r.qb << 8 | lane};
     }
     wave_sync();
     if (m == 0) return 0;
@@ -1342,10 +1165,10 @@ __device__ int s2_dedup_nopatch(PeReg *a, int n, int max_chain_gap, int lane) {
     }
     bool keep = false;
     if (lane < m) {
-        const S2Key16 x = k2[lane];
+        const Key16 x = k2[lane];
         keep = lane == 0;
         if (lane > 0) {
-            const S2Key16 y = k2[lane - 1];
+            const Key16 y = k2[lane - 1];
             keep = !(x.y == y.y && x.x == y.x && (x.z >> 8) == (y.z >> 8));
         }
     }
@@ -1360,50 +1183,26 @@ __device__ int s2_dedup_nopatch(PeReg *a, int n, int max_chain_gap, int lane) {
     return mm;
 }
 
-// mem_matesw's window of direction r for a mate region starting at a_rb (the rescued read l_ms
-// long): [rb, re) clipped to the strand's half of the doubled text; true when bwa runs its SW there
+// mem_matesw's window of direction r for a mate region starting at a_rb: clipped to the strand's
+// half of the doubled text (the anchor is one reference, rid 0)
 __device__ __forceinline__ bool s2_mate_window(int64_t l_pac, const af_params &p, const S2Pes &pe, int r,
                                                int64_t a_rb, int l_ms, int64_t &rb, int64_t &re, int &rid) {
-    const bool is_rev = (r >> 1) != (r & 1);
-    const bool is_larger = !(r >> 1);
-    if (!is_rev) {
-        rb = is_larger ? a_rb + pe.low : a_rb - pe.high;
-        re = (is_larger ? a_rb + pe.high : a_rb - pe.low) + l_ms;
-    } else {
-        rb = (is_larger ? a_rb + pe.low : a_rb - pe.high) - l_ms;
-        re = is_larger ? a_rb + pe.high : a_rb - pe.low;
-    }
-    if (rb < 0) rb = 0;
-    if (re > l_pac << 1) re = l_pac << 1;
-    if (rb < re) {
-        const int64_t mid = (rb + re) >> 1;
+    return mate_window(l_pac, p, pe, r, a_rb, 0, l_ms, rb, re, rid, [l_pac](int64_t &b, int64_t &e, int &id) {
+        const int64_t mid = (b + e) >> 1;
         const int64_t fb = mid < l_pac ? 0 : l_pac, fe = mid < l_pac ? l_pac : l_pac << 1;
-        rb = rb > fb ? rb : fb;
-        re = re < fe ? re : fe;
-        rid = 0;
-    }
-    // (rb >= re keeps rid from an earlier direction, as bwa does; re - rb < min_seed_len then)
-    return rid == 0 && re - rb >= p.min_seed_len;
+        b = b > fb ? b : fb;
+        e = e < fe ? e : fe;
+        id = 0;
+    });
 }
 
-// that window's ksw_align2 for the rescued read's codes qc (strand of direction r)
+// that window's ksw_align2 for the rescued read's codes qc, in the pair's LDS
 __device__ __forceinline__ void s2_mate_ksw(const DevText &X, const af_params &p, const uint8_t *qc, int l_ms, int r,
                                             int64_t rb, int64_t re, int &sc, int &te, int &qe, int &tb, int &qb,
                                             int lane) {
     PeLds &E = g_pe;
-    const bool is_rev = (r >> 1) != (r & 1);
-    for (int x = lane; x < l_ms; x += 64) {
-        const int c = qc[is_rev ? l_ms - 1 - x : x];
-        E.rq[x] = (uint8_t)(is_rev ? (c < 4 ? 3 - c : 4) : c);
-    }
-    const bool staged = re - rb <= PE_TW;
-    if (staged)
-        for (int x = lane; x < (int)(re - rb); x += 64) E.tw[x] = X.T[rb + x];
-    wave_sync();
-    const int P = l_ms * p.a < 250 ? 16 : 8;
     SPROF(if (lane == 0) E.misc[7] += (int)(re - rb);)
-    s2_ksw_align2(E.rq, l_ms, staged ? E.tw : X.T + rb, (int)(re - rb), P, p.min_seed_len * p.a, p, sc, te, qe, tb, qb,
-                  lane);
+    mate_ksw(X.T, p, qc, l_ms, r, rb, re, E.rq, E.tw, E.rq2, sc, te, qe, tb, qb, lane);
 }
 
 // mem_matesw (oracle mem_matesw): rescue read mi in the insert-size window of a region at a_rb
@@ -1419,7 +1218,7 @@ __device__ bool s2_matesw(const DevText &X, const af_params &p, const S2Opt &o, 
     for (int r = 0; r < 4; ++r) skip[r] = E.pes[r].failed ? 1 : 0;
     for (int i = 0; i < E.na[mi]; ++i) {
         int64_t dist;
-        const int r = s2_infer_dir(l_pac, a_rb, E.a[mi][i].r.rb, &dist);
+        const int r = infer_dir(l_pac, a_rb, E.a[mi][i].r.rb, &dist);
         if (dist >= E.pes[r].low && dist <= E.pes[r].high) skip[r] = 1;
     }
     if (skip[0] + skip[1] + skip[2] + skip[3] == 4) return true;
@@ -1430,7 +1229,7 @@ __device__ bool s2_matesw(const DevText &X, const af_params &p, const S2Opt &o, 
     bool deduped = false, dirty = false;
     for (int r = 0; r < 4; ++r) {
         if (skip[r]) continue;
-        const bool is_rev = (r >> 1) != (r & 1);
+        const bool is_rev = mate_is_rev(r);
         int64_t rb, re;
         if (s2_mate_window(l_pac, p, E.pes[r], r, a_rb, l_ms, rb, re, rid)) {
             int sc, te, qe, tb, qb;
@@ -1457,10 +1256,7 @@ __device__ bool s2_matesw(const DevText &X, const af_params &p, const S2Opt &o, 
                     for (int c = 0; c < PE_W8; ++c) reinterpret_cast<uint2 *>(ma + lane + 1)[c] = t[c];
                 if (lane == 0) {
                     PeReg b{};
-                    b.r.qb = is_rev ? l_ms - (qe + 1) : qb;
-                    b.r.qe = is_rev ? l_ms - qb : qe + 1;
-                    b.r.rb = is_rev ? (l_pac << 1) - (rb + te + 1) : rb + tb;
-                    b.r.re = is_rev ? (l_pac << 1) - (rb + tb) : rb + te + 1;
+                    mate_region_span(b.r, l_pac, is_rev, rb, l_ms, te, qe, tb, qb);
                     b.r.score = sc;
                     b.r.truesc = 0; b.r.w = 0; b.r.seedlen0 = 0;
                     b.secondary = -1;
@@ -1488,25 +1284,20 @@ __device__ bool s2_matesw(const DevText &X, const af_params &p, const S2Opt &o, 
 
 // mem_mark_primary_se (no ALT contigs) on the wave: the sort by (score desc, hash) over keys as in
 // s2_dedup_nopatch, the kept-hit walk on lane 0
-struct S2KeyHash {  // x = hash, y = score, z = index
-    __device__ bool operator()(const S2Key16 &a, const S2Key16 &b) const {
-        return a.y > b.y || (a.y == b.y && (uint64_t)a.x < (uint64_t)b.x);
-    }
-};
 __device__ void s2_mark_primary(PeReg *a, int n, int64_t id, const af_params &p, int lane) {
     if (n == 0) return;
     PeLds &E = g_pe;
-    S2Key16 *k = reinterpret_cast<S2Key16 *>(E.v), *t = k + AF_S2_MAX_REG;
+    Key16 *k = reinterpret_cast<Key16 *>(E.v), *t = k + AF_S2_MAX_REG;
     if (lane < n) {
         a[lane].secondary = -1;
         a[lane].hash = hash_64((uint64_t)(id + lane));
-        k[lane] = S2Key16{(int64_t)a[lane].hash, a[lane].r.score, lane};
+        k[lane] = Key16{(int64_t)a[lane].hash, a[lane].r.score, lane};
     }
     __threadfence_block();
     wave_sync();
     if (n > 1) {
-        if (!wave_rank_sort(k, n, S2KeyHash(), t, lane)) {
-            if (lane == 0) ks_introsort(k, n, S2KeyHash());
+        if (!wave_rank_sort(k, n, KeyHash(), t, lane)) {
+            if (lane == 0) ks_introsort(k, n, KeyHash());
             wave_sync();
         }
         s2_regs_gather(a, n, [&](int x) { return k[x].z; }, lane);
@@ -1519,12 +1310,7 @@ __device__ void s2_mark_primary(PeReg *a, int n, int64_t id, const af_params &p,
             int kk;
             for (kk = 0; kk < nz; ++kk) {
                 const int j = z[kk];
-                const int b_max = a[j].r.qb > a[i].r.qb ? a[j].r.qb : a[i].r.qb;
-                const int e_min = a[j].r.qe < a[i].r.qe ? a[j].r.qe : a[i].r.qe;
-                if (e_min > b_max) {
-                    const int min_l = a[i].r.qe - a[i].r.qb < a[j].r.qe - a[j].r.qb ? a[i].r.qe - a[i].r.qb : a[j].r.qe - a[j].r.qb;
-                    if ((float)(e_min - b_max) >= (float)min_l * 0.5f) break;
-                }
+                if (q_overlap_half(a[j].r.qb, a[j].r.qe, a[i].r.qb, a[i].r.qe)) break;
             }
             if (kk == nz) z[nz++] = i;
             else a[i].secondary = z[kk];
@@ -1534,11 +1320,8 @@ __device__ void s2_mark_primary(PeReg *a, int n, int64_t id, const af_params &p,
     wave_sync();
 }
 
-struct LtP64 {
-    __device__ bool operator()(const P64 &a, const P64 &b) const { return a.x < b.x || (a.x == b.x && a.y < b.y); }
-};
-
-// mem_pair (oracle mem_pair), lane 0: the best pair's score (0 if none) and z[]
+// mem_pair (oracle mem_pair), lane 0: the best pair's score (0 if none) and z[].  The anchor is
+// one reference: a key's position is the region's strand-folded start
 __device__ int s2_mem_pair(int64_t l_pac, const af_params &p, const S2Pes *pes, int id, int z[2]) {
     PeLds &E = g_pe;
     P64 *v = E.v;
@@ -1546,42 +1329,9 @@ __device__ int s2_mem_pair(int64_t l_pac, const af_params &p, const S2Pes *pes, 
     for (int r = 0; r < 2; ++r)
         for (int i = 0; i < E.na[r]; ++i) {
             const S2Reg &e = E.a[r][i].r;
-            P64 key;
-            key.x = (uint64_t)(e.rb < l_pac ? e.rb : (l_pac << 1) - 1 - e.rb);
-            key.y = (uint64_t)(uint32_t)e.score << 32 | (uint64_t)i << 2 | (uint64_t)(e.rb >= l_pac) << 1 | (uint64_t)r;
-            v[nv++] = key;
+            v[nv++] = mem_pair_key((uint64_t)(e.rb < l_pac ? e.rb : (l_pac << 1) - 1 - e.rb), e.score, i, e.rb >= l_pac, r);
         }
-    ks_introsort(v, nv, LtP64());
-    int y[4] = {-1, -1, -1, -1};
-    bool have = false;
-    P64 best{0, 0};
-    for (int i = 0; i < nv; ++i) {
-        for (int r = 0; r < 2; ++r) {
-            const int dir = r << 1 | (int)(v[i].y >> 1 & 1);
-            if (pes[dir].failed) continue;
-            const int which = r << 1 | (int)((v[i].y & 1) ^ 1);
-            if (y[which] < 0) continue;
-            for (int k = y[which]; k >= 0; --k) {
-                if ((int)(v[k].y & 3) != which) continue;
-                const int64_t dist = (int64_t)v[i].x - (int64_t)v[k].x;
-                if (dist > pes[dir].high) break;
-                if (dist < pes[dir].low) continue;
-                const double ns = ((double)dist - pes[dir].avg) / pes[dir].std;
-                int q = (int)((double)((v[i].y >> 32) + (v[k].y >> 32)) + .721 * log(2. * erfc(fabs(ns) * 0.70710678118654752440)) * p.a + .499);
-                if (q < 0) q = 0;
-                P64 u;
-                u.y = (uint64_t)k << 32 | (uint64_t)i;
-                u.x = (uint64_t)q << 32 | (hash_64(u.y ^ (uint64_t)(int64_t)(int32_t)((uint32_t)id << 8)) & 0xffffffffU);
-                if (!have || LtP64()(best, u)) { best = u; have = true; }
-            }
-        }
-        y[v[i].y & 3] = i;
-    }
-    if (!have) return 0;
-    const int i = (int)(best.y >> 32), k = (int)(best.y << 32 >> 32);
-    z[v[i].y & 1] = (int)(v[i].y << 32 >> 34);
-    z[v[k].y & 1] = (int)(v[k].y << 32 >> 34);
-    return (int)(best.x >> 32);
+    return mem_pair_scan(v, nv, pes, p, id, z);
 }
 
 // K3c: mem_sam_pe up to the record choice for every listed pair (one wave per pair): mate
@@ -1658,7 +1408,7 @@ __global__ __launch_bounds__(64, 4) void k_s2_pairs(DevText X, const uint8_t *__
             for (int k = lane; k < na; k += 64) E.a[m][k].r = w.pool[mp.x + k];
             if (lane == 0) { E.len[m] = l; E.na[m] = na; E.ovf[m] = mp.y < 0; }
         }
-        if (lane < 4) E.pes[lane] = w.pes[(int64_t)s2_chunk_of(w, pp) * 4 + lane];
+        if (lane < 4) E.pes[lane] = w.pes[(int64_t)chunk_of(w, pp) * 4 + lane];
         wave_sync();
         // mate rescue for the top hits of each end
         if (lane == 0) {
@@ -1748,7 +1498,7 @@ __global__ __launch_bounds__(64, 4) void k_s2_pairs(DevText X, const uint8_t *__
                 for (int i = 0; i < 2; ++i) which[i] = (E.na[i] && E.a[i][0].r.score >= p.T) ? 0 : -1;
                 if (which[0] >= 0 && which[1] >= 0) {
                     int64_t dist;
-                    const int d = s2_infer_dir(l_pac, E.a[0][0].r.rb, E.a[1][0].r.rb, &dist);
+                    const int d = infer_dir(l_pac, E.a[0][0].r.rb, E.a[1][0].r.rb, &dist);
                     if (!E.pes[d].failed && dist >= E.pes[d].low && dist <= E.pes[d].high) extra |= 2;
                 }
             }
@@ -1811,7 +1561,7 @@ __global__ __launch_bounds__(64, 4) void k_s2_pe_jobs(DevText X, const uint8_t *
             E.q[0][x] = ch == 'A' || ch == 'a' ? 0 : ch == 'C' || ch == 'c' ? 1 : ch == 'G' || ch == 'g' ? 2
                       : ch == 'T' || ch == 't' ? 3 : 4;
         }
-        if (lane < 4) E.pes[lane] = w.pes[(int64_t)s2_chunk_of(w, pp) * 4 + lane];
+        if (lane < 4) E.pes[lane] = w.pes[(int64_t)chunk_of(w, pp) * 4 + lane];
         // a_rb: end i's j-th region scoring within pen_unpaired of its best (K3c's list)
         const int64_t ri = 2 * pp + i;
         const int h = hits[ri];
@@ -2025,7 +1775,24 @@ __global__ __launch_bounds__(1024) void k_s2_chunks(int64_t n_pairs, int32_t str
     }
 }
 
+// test hook (af_debug_kbtree, store 0): the shared kbtree over the S2 store, keys pos[0, n)
+__global__ __launch_bounds__(64) void k_debug_kbtree_s2(const int64_t *__restrict__ pos, int n,
+                                                        int32_t *__restrict__ lower, int32_t *__restrict__ order,
+                                                        int32_t *__restrict__ count) {
+    if (threadIdx.x != 0) return;
+    for (int i = 0; i < n; ++i) g_s2.ch[i].pos = (int32_t)pos[i];
+    g_s2.cnt[6] = 0;
+    S2Tree tree;
+    *count = kb_debug_fill(tree, n, lower, order);
+}
+
 }  // namespace
+
+// n <= AF_S2_MAX_CHAIN keys that fit the store's 32-bit positions (checked by af_debug_kbtree)
+hipError_t af_launch_debug_kbtree_s2(const int64_t *pos, int n, int32_t *lower, int32_t *order, int32_t *count) {
+    hipLaunchKernelGGL(k_debug_kbtree_s2, dim3(1), dim3(64), 0, 0, pos, n, lower, order, count);
+    return hipGetLastError();
+}
 
 #ifdef AF_K2_PROF
 extern "C" int af_debug_s2_prof_enable() {

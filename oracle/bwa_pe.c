@@ -1039,6 +1039,32 @@ static void kb_traverse(const kbtree_t *b, int xi, int *out, int *n) {
     if (x->internal) kb_traverse(b, x->ptr[x->n], out, n);
 }
 
+/* test hook: chains 0..n-1 with keys pos[] inserted in turn into an empty tree; lower[i] =
+ * kb_lower(pos[i]) before chain i goes in (-1 on the empty tree), order[] = the final in-order
+ * traversal.  Returns 0, -1 on bad arguments or no memory (every non-root node holds >= KB_T - 1
+ * keys, so n + 8 nodes never run out). */
+int afo_debug_kbtree(const int64_t *pos, int n, int32_t *lower, int32_t *order) {
+    if (n < 1 || n > AFO_G_MAX_CHAIN || !pos || !lower || !order) return -1;
+    chain_t *ch = (chain_t *)calloc((size_t)n, sizeof(chain_t));
+    kbnode_t *nodes = (kbnode_t *)malloc(sizeof(kbnode_t) * ((size_t)n + 8));
+    int *out = (int *)malloc(sizeof(int) * (size_t)n);
+    int no = 0, rc = -1;
+    if (ch && nodes && out) {
+        kbtree_t tree;
+        kb_init(&tree, nodes, ch);
+        for (int i = 0; i < n; ++i) {
+            ch[i].pos = pos[i];
+            lower[i] = i ? kb_lower(&tree, pos[i]) : -1;
+            kb_putp(&tree, i);
+        }
+        kb_traverse(&tree, tree.root, out, &no);
+        for (int i = 0; i < no; ++i) order[i] = out[i];
+        rc = no == n ? 0 : -1;
+    }
+    free(ch); free(nodes); free(out);
+    return rc;
+}
+
 /* ============================================================= mem_chain / mem_chain_flt */
 /* chain storage during mem_chain: each chain's seeds in a per-chain list (linked through the
  * pool); compacted per chain afterwards */

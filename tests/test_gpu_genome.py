@@ -134,6 +134,39 @@ def test_wave_introsort_equals_klib():
             assert np.all(np.diff((a >> np.uint64(32)).astype(np.int64)) <= 0)
 
 
+def test_kbtree_equals_klib():
+    """bwa_mem_dev.h's one kbtree (mem_chain's tree of chains) on both of its stores -- the S2 store
+    in LDS (store 0) and the genome store with its LDS / scratch split (store 1) -- against klib's
+    (oracle afo_debug_kbtree), through the test hook af_debug_kbtree: every kb_lower answer along
+    the insertions and the final traversal, exactly.  Key sets with ties everywhere (where the
+    tree's shape, so the post-split descent, decides the answers) and sizes around the S2 store's
+    first root split and cap and the genome store's LDS limits: tests/kbtree_cases.py."""
+    import ctypes
+    import kbtree_cases as kc
+    from anchored_fusion_amd import _lib
+    L = _lib.lib()
+    L.af_debug_kbtree.restype = ctypes.c_int
+    L.af_debug_kbtree.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    for store, kind, n in kc.cases():
+        pos = kc.keys(store, kind, n)
+        rc, want_lower, want_order = kc.oracle_answer(store, kind, n)
+        assert rc == 0, (store, kind, n)
+        lower = np.full(n, -9, np.int32)
+        order = np.full(n, -9, np.int32)
+        assert L.af_debug_kbtree(pos.ctypes.data, n, store, lower.ctypes.data, order.ctypes.data) == 0, (store, kind, n)
+        assert np.array_equal(lower, want_lower), (store, kind, n, np.nonzero(lower != want_lower)[0][:5])
+        assert np.array_equal(order, want_order), (store, kind, n, np.nonzero(order != want_order)[0][:5])
+    # the argument checks answer before any launch
+    one = np.zeros(64, np.int64)
+    out = np.zeros(64, np.int32)
+    assert L.af_debug_kbtree(one.ctypes.data, 0, 0, out.ctypes.data, out.ctypes.data) == -1
+    assert L.af_debug_kbtree(one.ctypes.data, 33, 0, out.ctypes.data, out.ctypes.data) == -1
+    assert L.af_debug_kbtree(one.ctypes.data, 8, 2, out.ctypes.data, out.ctypes.data) == -1
+    assert L.af_debug_kbtree(None, 8, 1, out.ctypes.data, out.ctypes.data) == -1
+    one[3] = 1 << 31
+    assert L.af_debug_kbtree(one.ctypes.data, 8, 0, out.ctypes.data, out.ctypes.data) == -1
+
+
 def test_se_records_equal_oracle(world):
     contigs, og, gg = world
     reads, lens = sample_reads(contigs, 600, seed=22, chimeric=0.4)

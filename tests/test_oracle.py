@@ -171,3 +171,30 @@ def test_tandem_repeat_runs(anchor, oidx):
     reads = tandem_pairs(anchor)
     out = oidx.align_pairs(reads, threads=4)
     assert len(out["flag"]) == reads.shape[0]
+
+
+def test_kbtree_hook_is_klib_on_every_case():
+    """afo_debug_kbtree (klib's kbtree as mem_chain drives it) handles every key set of
+    tests/kbtree_cases.py, the GPU test's reference: the traversal is a permutation in key order,
+    each kb_lower answer holds the largest key at or below the probe among the chains already in;
+    with distinct keys that pins both outputs (the argsort, the predecessor)."""
+    import kbtree_cases as kc
+    for store, kind, n in kc.cases():
+        pos = kc.keys(store, kind, n)
+        rc, lower, order = kc.oracle_answer(store, kind, n)
+        assert rc == 0, (store, kind, n)
+        assert np.array_equal(np.sort(order), np.arange(n)), (store, kind, n)
+        assert np.all(np.diff(pos[order]) >= 0), (store, kind, n)
+        assert lower[0] == -1
+        for i in range(1, n):
+            below = pos[:i][pos[:i] <= pos[i]]
+            if below.size == 0:
+                assert lower[i] == -1, (store, kind, n, i)
+            else:
+                assert 0 <= lower[i] < i and pos[lower[i]] == below.max(), (store, kind, n, i)
+        if kind in ("distinct", "ascending", "descending"):
+            assert len(set(pos.tolist())) == n
+            assert np.array_equal(order, np.argsort(pos, kind="stable")), (store, kind, n)
+            pred = [-1] + [int(np.nonzero(pos[:i] == pos[:i][pos[:i] < pos[i]].max())[0][0])
+                           if (pos[:i] < pos[i]).any() else -1 for i in range(1, n)]
+            assert np.array_equal(lower, np.array(pred, np.int32)), (store, kind, n)
