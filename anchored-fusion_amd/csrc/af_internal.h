@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <vector>
 #include "../../include/afgpu.h"
+#include "dev_buf.h"
 
 #define AF_NEG_INF (-0x40000000)
 #define AF_SEED_BTILE 2048      // reads per workgroup tile in the seed filter
@@ -454,7 +455,7 @@ size_t af_blat_order_bytes(int64_t cap);
 hipError_t af_launch_blat_order(const DevTile &X, const uint8_t *queries, const int32_t *n_queries, int64_t cap,
                                 int32_t stride, const int32_t *lens, int32_t rep_match, void *work,
                                 int32_t *order, hipStream_t s);
-hipError_t af_build_tile_index(const uint8_t *d_seq, int64_t n, int32_t step, DevTile *X, void **allocs, int *na,
+hipError_t af_build_tile_index(const uint8_t *d_seq, int64_t n, int32_t step, DevTile *X, DevBufList &owned,
                                hipStream_t s);
 hipError_t af_launch_clamp_count(const int32_t *count, int64_t cap, int32_t *dst, hipStream_t s);
 // s3.hip: S3 (samtools sort + flag filters) on the device

@@ -12,114 +12,125 @@
 #include <string>
 #include <vector>
 
+// One GPeSpec pool (heavy pairs whose rescue SWs run as grid jobs): S2's K3c and S4 each own one
+struct PeSpecBufs {
+    DevBuf<int32_t> pair, off, nj, res;
+    DevBuf<int2> job;
+    DevBuf<unsigned long long> cnt;  // allocated once
+    GPeSpec view(int32_t min_windows) const {
+        GPeSpec e;
+        e.pair = pair; e.off = off; e.nj = nj; e.job = job; e.res = res; e.cnt = cnt;
+        e.cap_pairs = pair.size(); e.cap_jobs = job.size();
+        e.min_windows = cnt && pair ? min_windows : 0;  // no pool (a failed regrow): every pair on its own wave
+        return e;
+    }
+};
+
+// The per-chunk insert-size statistics (k_s2_pestat): S2 and S4 each own a set
+struct ChunkStatBufs {
+    DevBuf<S2Pes> pes;        // [max_chunks][4]
+    DevBuf<int64_t> cstart;   // [max_chunks + 1]
+    DevBuf<int32_t> nchunks;  // one word
+    DevBuf<int32_t> ghist;    // [max_chunks][4][max_ins + 1], zero-filled, zero between calls
+    int32_t max_chunks() const { return (int32_t)(pes.size() / 4); }
+};
+
+// Every device buffer of a context is a DevBuf member (dev_buf.h): its size is its capacity, the
+// destructor frees it.  The kernel-argument structs (S2Work, GWork, BlatLaunch, ...) are views
+// filled from these members where a call is set up.
 struct af_ctx {
     int device = 0;
     int n_cu = 0;
     int n_slots = 0;
     std::string err;
     // scratch (device)
-    int32_t *ctrl = nullptr;   // af_internal.h: candidate counts (2 epochs) + K2 dequeue heads
+    DevBuf<int32_t> ctrl;      // af_internal.h: candidate counts (2 epochs) + K2 dequeue heads; zero-filled
     int64_t epoch = 0;         // seed-filter calls so far; the last call used count slot (epoch - 1) & 1
-    int32_t *cand = nullptr;
-    uint32_t *d_packed = nullptr;  // af_align_pairs: the candidates' CIGAR rows, gathered for one D2H
-    int64_t cap_packed = 0;
-    int64_t cap_reads = 0;
-    uint8_t *zscratch = nullptr;
-    uint8_t *bscratch = nullptr;  // k_blat: AF_BLAT_SLOT_BYTES per resident wave (blat_slots)
-    int blat_slots = 0;
-    void *blat_ord_work = nullptr;  // k_blat's cost-ordered schedule (af_launch_blat_order)
-    int32_t *blat_order = nullptr;
-    int64_t blat_ord_cap = 0;
-    int32_t *blat_caps = nullptr;   // AF_BLAT_CAP_N counters, cumulative until af_blat_caps resets them
-    BlatSpill blat_spill;           // af_blat_spill's pool (caller-owned device buffers)
-    int32_t *blat_qcaps = nullptr;  // af_blat_query_caps' per-query counters (caller-owned), their query capacity
+    DevBuf<int32_t> cand;      // one per read of the seed filter's batch
+    DevBuf<uint32_t> d_packed; // af_align_pairs: the candidates' CIGAR rows, gathered for one D2H
+    DevBuf<uint8_t> zscratch;  // allocated once
+    DevBuf<uint8_t> bscratch;  // k_blat: AF_BLAT_SLOT_BYTES per resident wave
+    DevBuf<uint8_t> blat_ord_work;  // k_blat's cost-ordered schedule (af_launch_blat_order)
+    DevBuf<int32_t> blat_order;
+    DevBuf<int32_t> blat_caps;      // AF_BLAT_CAP_N counters (zero-filled), cumulative until af_blat_caps resets them
+    BlatSpill blat_spill;           // af_blat_spill's pool: borrowed, the caller owns the device buffers
+    int32_t *blat_qcaps = nullptr;  // af_blat_query_caps' per-query counters: borrowed; their query capacity
     int64_t blat_qcap = 0;
-    BlatHeavy blat_hv;              // the deferred strands' table
+    DevBuf<int4> blat_hv_strands;   // the deferred strands' table (BlatHeavy) and its control words
+    DevBuf<int32_t> blat_hv_ctrl;
     int32_t blat_heavy_min = AF_BLAT_HEAVY_CLUMPS;
     BlatLaunch blat_pending;        // af_blat_device_begin's search, finished by af_blat_device_end
     bool blat_open = false;
-    af_psl *blat_stage = nullptr;   // per (query, strand) rows before k_blat_merge
-    int32_t *blat_stage_n = nullptr;
-    int64_t blat_stage_rows = 0, blat_stage_items = 0;
-    // S2 (bwa mem paired-end) scratch, s2.hip
-    S2Reg *s2_pool = nullptr;
-    int64_t s2_pool_cap = 0;
-    int2 *s2_rmap = nullptr;
-    int32_t *s2_plist = nullptr, *s2_ghist = nullptr;
-    int64_t s2_ghist_ints = 0;
-    int64_t *s2_scan = nullptr;
-    void *s2_plan = nullptr;
-    int64_t s2_cap_pairs = 0;
-    int32_t *s2_nchunks = nullptr;
-    S2Pes *s2_pes = nullptr;
-    int64_t *s2_cstart = nullptr;
-    int32_t s2_max_chunks = 0;
-    // S3 (s3.hip)
-    uint64_t *s3_keys = nullptr;
-    void *s3_temp = nullptr;
-    int64_t s3_cap = 0;
+    DevBuf<af_psl> blat_stage;      // per (query, strand) rows before k_blat_merge
+    DevBuf<int32_t> blat_stage_n;
+    // S2 (bwa mem paired-end) scratch, s2.hip: the region pool and the per-pair arrays share one capacity
+    DevBuf<S2Reg> s2_pool;
+    DevBuf<int2> s2_rmap;
+    DevBuf<int32_t> s2_plist;
+    DevBuf<int64_t> s2_scan;
+    DevBuf<uint8_t> s2_plan;
+    ChunkStatBufs s2_cs;
+    PeSpecBufs s2_sp;
+    int32_t s2_sp_min = AF_S2_SPEC_WINDOWS;
+    // S3 (s3.hip): both key halves in one allocation, the second at + size() / 2
+    DevBuf<uint64_t> s3_keys;
+    DevBuf<uint8_t> s3_temp;
     size_t s3_temp_bytes = 0;
-    int64_t *s3_counts = nullptr;
-    int32_t *g_sel = nullptr;   // af_gather_reads_device: selected rows, their count, select scratch
-    int64_t *g_sel_n = nullptr;
-    void *g_temp = nullptr;
-    int64_t g_cap = 0;
+    DevBuf<int64_t> s3_counts;  // allocated once
+    DevBuf<int32_t> g_sel;      // af_gather_reads_device: selected rows, their count (allocated once), select scratch
+    DevBuf<int64_t> g_sel_n;
+    DevBuf<uint8_t> g_temp;
     size_t g_temp_bytes = 0;
     // host-API staging (device)
-    uint8_t *d_reads = nullptr;
-    int64_t cap_bytes = 0;
-    int32_t *d_lens = nullptr;
-    int32_t *d_flag = nullptr, *d_pos = nullptr, *d_score = nullptr, *d_ncig = nullptr, *d_hits = nullptr;
-    uint32_t *d_cigar = nullptr;
-    int64_t cap_out = 0;
+    DevBuf<uint8_t> d_reads;
+    DevBuf<int32_t> d_lens;
+    DevBuf<int32_t> d_flag, d_pos, d_score, d_ncig, d_hits;
+    DevBuf<uint32_t> d_cigar;
     hipStream_t stream = nullptr;
-    // the genome calls S4 / S5 (bwa_genome.hip): per-lane / per-wave scratch, per-call pools
-    uint8_t *g1_scr = nullptr, *g2_scr = nullptr;
+    // the genome calls S4 / S5 (bwa_genome.hip): per-lane / per-wave scratch (allocated once), per-call pools
+    DevBuf<uint8_t> g1_scr, g2_scr;
     int g1_threads = 0, g2_waves = 0;
     // the paired-end records beside the single-end ones (af_genome_align_pe_se_device): their own
     // per-wave scratch, and the event that orders them after the shared seed / region kernels
-    uint8_t *g2_scr_pe = nullptr, *zscratch_pe = nullptr;
+    DevBuf<uint8_t> g2_scr_pe, zscratch_pe;
     hipEvent_t g_ev = nullptr;
     // G2's heavy-read pools (GHeavy) and the kept-chain count from which a read is heavy
-    GHeavy g_hv{};
+    DevBuf<int64_t> hv_read;
+    DevBuf<int32_t> hv_nch, hv_ch_off, hv_sd_off, hv_ch_read;
+    DevBuf<uint8_t> hv_ch, hv_sd;  // GChain [cap_ch], GSeed [cap_sd]
+    DevBuf<GReg> hv_res;
+    DevBuf<unsigned long long> hv_cnt;  // allocated once
     int32_t g_heavy_min = AF_G_HEAVY_CHAINS;
-    GPeSpec g_pe{};
+    PeSpecBufs g_pe;
     int32_t g_pe_min = AF_G_PE_SPEC_WINDOWS;
-    GPeSpec s2_sp{};
-    int32_t s2_sp_min = AF_S2_SPEC_WINDOWS;
     int32_t g1_max_ext = AF_G1_HEAVY_EXT;
     bool g1_ext_env = false;        // AF_G1_HEAVY_EXT given: the hand-off threshold is fixed
     // G2 takes the reads with at least this many seeds first (env AF_G2_FIRST_OCC; 0: read order)
     int32_t g2_first_occ = AF_G2_FIRST_OCC;
-    int32_t *g2_list = nullptr;
-    uint8_t *g2_flag = nullptr;
-    int64_t *g1_hv = nullptr;       // G1's heavy-read list (ensure_genome_pools)
-    GIv *g_iv = nullptr;
-    GReg *g_reg = nullptr;
-    int64_t g_iv_cap = 0, g_reg_cap = 0, g_cap_reads = 0;
-    unsigned long long *g_iv_fill = nullptr;
-    int32_t *g_reg_fill = nullptr, *g_stats = nullptr, *g_iv_n = nullptr, *g_reg_off = nullptr, *g_reg_n = nullptr;
-    int64_t *g_iv_off = nullptr;
-    int32_t *g_ghist = nullptr, *g_nchunks = nullptr;
-    int64_t g_ghist_ints = 0, *g_cstart = nullptr, *g_scan = nullptr, g_scan_cap = 0;
-    S2Pes *g_pes = nullptr;
-    int32_t g_max_chunks = 0;
-    af_grec *g_recs = nullptr;      // host-buffer API staging
-    int32_t *g_nrec = nullptr, *g_hlens = nullptr;
-    uint8_t *g_hreads = nullptr;
-    int64_t g_cap_recs = 0, g_cap_hbytes = 0;
+    DevBuf<int32_t> g2_list;
+    DevBuf<uint8_t> g2_flag;
+    DevBuf<int64_t> g1_hv;          // G1's heavy-read list (ensure_genome_pools)
+    DevBuf<GIv> g_iv;               // the interval and region pools; the per-read arrays below share g_iv_off's capacity
+    DevBuf<GReg> g_reg;
+    DevBuf<int64_t> g_iv_off;
+    DevBuf<int32_t> g_iv_n, g_reg_off, g_reg_n;
+    DevBuf<unsigned long long> g_iv_fill;  // allocated once, as g_reg_fill and the zero-filled g_stats
+    DevBuf<int32_t> g_reg_fill, g_stats;
+    ChunkStatBufs g_cs;
+    DevBuf<int64_t> g_scan;
+    DevBuf<af_grec> g_recs;         // host-buffer API staging
+    DevBuf<int32_t> g_nrec, g_hlens;
+    DevBuf<uint8_t> g_hreads;
     // the S5 genome check + S6 queries (s5s6.hip)
-    uint8_t *s5_keep = nullptr;
-    int32_t *s5_sel = nullptr;
-    int64_t *s5_nsel = nullptr;
-    void *s5_temp = nullptr;
+    DevBuf<uint8_t> s5_keep;
+    DevBuf<int32_t> s5_sel;
+    DevBuf<int64_t> s5_nsel;        // allocated once
+    DevBuf<uint8_t> s5_temp;
     size_t s5_temp_bytes = 0;
-    int64_t s5_cap = 0;
     // af_s6_compact_device: the pre rows' survivor flags and new indices, the spill pool's, scan scratch
-    int32_t *s6_flag = nullptr, *s6_idx = nullptr, *s6_sflag = nullptr, *s6_sidx = nullptr;
-    void *s6_temp = nullptr;
+    DevBuf<int32_t> s6_flag, s6_idx, s6_sflag, s6_sidx;
+    DevBuf<uint8_t> s6_temp;
     size_t s6_temp_bytes = 0;
-    int64_t s6_cap = 0, s6_spill_cap = 0;
 };
 
 struct af_genome {
@@ -138,15 +149,10 @@ struct af_index {
     bool s2_ready = false;
     DevTile tile{};        // BLAT tile index (af_tile_index_build*), else unused
     bool is_tile = false;
-    void *allocs[24] = {};
-    int n_allocs = 0;
+    DevBufList owned;      // every device array dev / s2 / tile point to
 };
 
 namespace {
-
-inline void af_free(void *p) {
-    if (p) (void)hipFree(p);
-}
 
 int fail(af_ctx *c, int code, const char *fmt, ...) {
     char buf[512];
@@ -162,6 +168,15 @@ int fail(af_ctx *c, int code, const char *fmt, ...) {
     do {                                                                                        \
         hipError_t _e = (expr);                                                                 \
         if (_e != hipSuccess) return fail(ctx, AF_E_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+// The one report of a failed device allocation (a DevBuf grow / alloc, dev_alloc_all, dev_list_alloc):
+// `code` is what the entry point returns for it, AF_E_HIP unless it has always said AF_E_NOMEM.  The
+// buffers concerned are empty afterwards, so no stale pointer or capacity outlives the failure.
+#define ALLOCCHK(ctx, code, expr)                                                                           \
+    do {                                                                                                    \
+        hipError_t _e = (expr);                                                                             \
+        if (_e != hipSuccess) return fail(ctx, code, "device allocation %s: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
 // CIGAR rows of the reads of the listed pairs (the only rows the pair kernel writes), row i =
@@ -237,71 +252,104 @@ std::vector<int32_t> suffix_ranks(const std::vector<uint8_t> &T) {
 
 template <class T>
 int dev_upload(af_ctx *ctx, af_index *ix, const std::vector<T> &v, const T **out) {
-    void *p = nullptr;
-    const size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
-    HIPCHK(ctx, hipMalloc(&p, bytes));
-    ix->allocs[ix->n_allocs++] = p;
+    T *p = nullptr;
+    ALLOCCHK(ctx, AF_E_HIP, dev_list_alloc(ix->owned, std::max<size_t>(v.size() * sizeof(T), 16), &p));
     if (!v.empty()) HIPCHK(ctx, hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = static_cast<const T *>(p);
+    *out = p;
     return AF_OK;
 }
 
+// The 16-mer position table of a code array (codes & 3, two bits per base): the positions p with
+// p + AF_K <= size and !skip(p) grouped by 16-mer, ascending (kpos), and the open-addressed hash of
+// the distinct 16-mers (hslot, 2^hbits slots: {key, first index into kpos, count, kpos[first]})
+struct KmerTable {
+    std::vector<int4> hslot;
+    std::vector<int32_t> kpos;
+    int hbits = 10;
+};
+template <class Skip>
+KmerTable kmer_table(const std::vector<uint8_t> &codes, Skip skip) {
+    const int64_t N = (int64_t)codes.size();
+    std::vector<uint64_t> occ;
+    occ.reserve(N);
+    for (int64_t p = 0; p + AF_K <= N; ++p) {
+        if (skip(p)) continue;
+        uint32_t k = 0;
+        for (int u = 0; u < AF_K; ++u) k |= (uint32_t)(codes[p + u] & 3) << (2 * u);
+        occ.push_back((uint64_t)k << 32 | (uint64_t)p);
+    }
+    std::sort(occ.begin(), occ.end());
+    KmerTable t;
+    std::vector<uint32_t> keys;
+    std::vector<int32_t> starts, cnts;
+    t.kpos.resize(occ.size());
+    for (size_t i = 0; i < occ.size(); ++i) {
+        const uint32_t k = (uint32_t)(occ[i] >> 32);
+        t.kpos[i] = (int32_t)(occ[i] & 0xffffffffu);
+        if (i == 0 || k != keys.back()) { keys.push_back(k); starts.push_back((int32_t)i); cnts.push_back(0); }
+        ++cnts.back();
+    }
+    const int64_t nd = (int64_t)keys.size();
+    while ((1LL << t.hbits) < 2 * nd) ++t.hbits;
+    const uint32_t hm = (1u << t.hbits) - 1u;
+    t.hslot.assign(1u << t.hbits, int4{0, 0, 0, 0});
+    for (int64_t i = 0; i < nd; ++i) {
+        uint32_t sl = af_fmix(keys[i]) & hm;
+        while (t.hslot[sl].z) sl = (sl + 1) & hm;
+        t.hslot[sl] = int4{(int)keys[i], starts[i], cnts[i], t.kpos[starts[i]]};
+    }
+    return t;
+}
+
 int ensure_reads_cap(af_ctx *c, int64_t n_reads) {
-    if (n_reads <= c->cap_reads) return AF_OK;
-    af_free(c->cand);
-    c->cand = nullptr; c->cap_reads = 0;
-    const int64_t cap = std::max<int64_t>(n_reads, 1 << 16);
-    HIPCHK(c, hipMalloc(&c->cand, sizeof(int32_t) * cap));
-    c->cap_reads = cap;
+    ALLOCCHK(c, AF_E_HIP, c->cand.grow(n_reads, 1 << 16));
     return AF_OK;
 }
 
 int ensure_zscratch(af_ctx *c) {
-    if (c->zscratch) return AF_OK;
-    const size_t zstride = (size_t)(AF_MAX_READ + 1) * 1024;
-    HIPCHK(c, hipMalloc(&c->zscratch, zstride * c->n_slots));
+    ALLOCCHK(c, AF_E_HIP, c->zscratch.grow((int64_t)(AF_MAX_READ + 1) * 1024 * c->n_slots));
     return AF_OK;
 }
 
 // the deferred strands' table for a search of cap queries (grow-only; a strand that does not fit
 // is searched by k_blat itself)
 int ensure_blat_heavy(af_ctx *c, int64_t cap) {
-    BlatHeavy &h = c->blat_hv;
-    h.min_clumps = c->blat_heavy_min;
-    if (h.min_clumps <= 0) return AF_OK;
+    if (c->blat_heavy_min <= 0) return AF_OK;
     const int64_t strands = std::min<int64_t>(1 << 16, std::max<int64_t>(1024, 2 * cap));
-    if (h.ctrl && h.strands_cap >= strands) return AF_OK;
-    if (h.ctrl) HIPCHK(c, hipDeviceSynchronize());  // an earlier search may still use the table
-    af_free(h.strands); af_free(h.ctrl);
-    h = BlatHeavy{};
-    h.min_clumps = c->blat_heavy_min;
-    HIPCHK(c, hipMalloc(&h.strands, sizeof(int4) * strands));
-    HIPCHK(c, hipMalloc(&h.ctrl, sizeof(int32_t) * AF_BLAT_HV_CTRL_WORDS));
-    h.strands_cap = strands;
-    h.jobs_n = h.ctrl + AF_BLAT_HV_JOBS_N;
-    h.strands_n = h.ctrl + AF_BLAT_HV_STRANDS_N;
+    if (c->blat_hv_ctrl && c->blat_hv_strands.size() >= strands) return AF_OK;
+    if (c->blat_hv_ctrl) HIPCHK(c, hipDeviceSynchronize());  // an earlier search may still use the table
+    ALLOCCHK(c, AF_E_HIP, dev_alloc_all({{c->blat_hv_strands, strands}, {c->blat_hv_ctrl, AF_BLAT_HV_CTRL_WORDS}}));
     return AF_OK;
 }
 
+BlatHeavy blat_heavy(const af_ctx *c) {
+    BlatHeavy h;
+    h.min_clumps = c->blat_heavy_min;
+    if (!c->blat_hv_ctrl) return h;
+    h.strands = c->blat_hv_strands;
+    h.strands_cap = c->blat_hv_strands.size();
+    h.ctrl = c->blat_hv_ctrl;
+    h.jobs_n = h.ctrl + AF_BLAT_HV_JOBS_N;
+    h.strands_n = h.ctrl + AF_BLAT_HV_STRANDS_N;
+    return h;
+}
+
 int ensure_blat_order(af_ctx *c, int64_t cap) {
-    if (cap <= c->blat_ord_cap) return AF_OK;
-    af_free(c->blat_ord_work); af_free(c->blat_order);
-    c->blat_ord_work = nullptr; c->blat_order = nullptr; c->blat_ord_cap = 0;
-    HIPCHK(c, hipMalloc(&c->blat_ord_work, af_blat_order_bytes(cap)));
-    HIPCHK(c, hipMalloc(&c->blat_order, sizeof(int32_t) * cap));
-    c->blat_ord_cap = cap;
+    if (cap <= c->blat_order.size()) return AF_OK;
+    ALLOCCHK(c, AF_E_HIP,
+             dev_alloc_all({{c->blat_ord_work, (int64_t)af_blat_order_bytes(cap)}, {c->blat_order, cap}}));
     return AF_OK;
 }
 
 int ensure_blat_stage(af_ctx *c, int64_t cap, int32_t max_rows) {
     const int64_t need = 2 * cap * max_rows;
-    if (c->blat_stage && need <= c->blat_stage_rows && 2 * cap <= c->blat_stage_items) return AF_OK;
-    af_free(c->blat_stage); af_free(c->blat_stage_n);
-    c->blat_stage = nullptr; c->blat_stage_n = nullptr; c->blat_stage_rows = c->blat_stage_items = 0;
-    HIPCHK(c, hipMalloc(&c->blat_stage, sizeof(af_psl) * need));
-    HIPCHK(c, hipMalloc(&c->blat_stage_n, sizeof(int32_t) * 2 * cap));
-    c->blat_stage_rows = need;
-    c->blat_stage_items = 2 * cap;
+    if (need <= c->blat_stage.size() && 2 * cap <= c->blat_stage_n.size()) return AF_OK;
+    ALLOCCHK(c, AF_E_HIP, dev_alloc_all({{c->blat_stage, need}, {c->blat_stage_n, 2 * cap}}));
+    return AF_OK;
+}
+
+int ensure_blat_caps(af_ctx *c) {
+    ALLOCCHK(c, AF_E_HIP, c->blat_caps.grow_zeroed(AF_BLAT_CAP_N));
     return AF_OK;
 }
 
@@ -310,19 +358,11 @@ int ensure_blat_stage(af_ctx *c, int64_t cap, int32_t max_rows) {
 // its own -- holds a few slots, not the 2 MB x 6,144 a genome-wide S6 needs)
 int ensure_bscratch(af_ctx *c, int64_t items) {
     const int max_slots = af_blat_slots(c->n_cu);
-    const int want = (int)std::min<int64_t>(max_slots, std::max<int64_t>(64, (items + 63) / 64 * 64));
-    if (!c->blat_caps) {
-        HIPCHK(c, hipMalloc(&c->blat_caps, sizeof(int32_t) * AF_BLAT_CAP_N));
-        HIPCHK(c, hipMemset(c->blat_caps, 0, sizeof(int32_t) * AF_BLAT_CAP_N));
-    }
-    if (c->bscratch && c->blat_slots >= want) return AF_OK;
-    if (c->bscratch) {
-        HIPCHK(c, hipDeviceSynchronize());  // an earlier search may still use the old slots
-        af_free(c->bscratch);
-        c->bscratch = nullptr;
-    }
-    c->blat_slots = want;
-    HIPCHK(c, hipMalloc(&c->bscratch, (size_t)AF_BLAT_SLOT_BYTES * c->blat_slots));
+    const int64_t want = std::min<int64_t>(max_slots, std::max<int64_t>(64, (items + 63) / 64 * 64));
+    if (int rc = ensure_blat_caps(c)) return rc;
+    if ((int64_t)AF_BLAT_SLOT_BYTES * want <= c->bscratch.size()) return AF_OK;
+    if (c->bscratch) HIPCHK(c, hipDeviceSynchronize());  // an earlier search may still use the old slots
+    ALLOCCHK(c, AF_E_HIP, c->bscratch.grow((int64_t)AF_BLAT_SLOT_BYTES * want));
     return AF_OK;
 }
 
@@ -336,41 +376,15 @@ int ensure_s2_text(af_ctx *c, af_index *ix) {
     std::vector<int32_t> rank = suffix_ranks(T);
     std::vector<uint32_t> T2((N + 15) / 16 + 2, 0);
     for (int64_t i = 0; i < N; ++i) T2[i >> 4] |= (uint32_t)T[i] << (2 * (i & 15));
-    std::vector<uint64_t> occ;
-    occ.reserve(N);
-    for (int64_t q = 0; q + AF_K <= N; ++q) {
-        uint32_t k = 0;
-        for (int u = 0; u < AF_K; ++u) k |= (uint32_t)T[q + u] << (2 * u);
-        occ.push_back((uint64_t)k << 32 | (uint64_t)q);
-    }
-    std::sort(occ.begin(), occ.end());
-    std::vector<uint32_t> keys;
-    std::vector<int32_t> starts, cnts, kpos(occ.size());
-    for (size_t i = 0; i < occ.size(); ++i) {
-        const uint32_t k = (uint32_t)(occ[i] >> 32);
-        kpos[i] = (int32_t)(occ[i] & 0xffffffffu);
-        if (i == 0 || k != keys.back()) { keys.push_back(k); starts.push_back((int32_t)i); cnts.push_back(0); }
-        ++cnts.back();
-    }
-    const int64_t nd = (int64_t)keys.size();
-    int hbits = 10;
-    while ((1LL << hbits) < 2 * nd) ++hbits;
-    const uint32_t hm = (1u << hbits) - 1u;
-    std::vector<int4> hslot(1u << hbits, int4{0, 0, 0, 0});
-    for (int64_t i = 0; i < nd; ++i) {
-        uint32_t sl = af_fmix(keys[i]) & hm;
-        while (hslot[sl].z) sl = (sl + 1) & hm;
-        hslot[sl] = int4{(int)keys[i], starts[i], cnts[i], kpos[starts[i]]};
-    }
-    if (ix->n_allocs + 5 > 24) return fail(c, AF_E_INVALID, "index allocation table full");
+    const KmerTable kt = kmer_table(T, [](int64_t) { return false; });
     int rc;
     DevText X{};
     if ((rc = dev_upload(c, ix, T, &X.T)) || (rc = dev_upload(c, ix, T2, &X.T2)) ||
-        (rc = dev_upload(c, ix, rank, &X.rank)) || (rc = dev_upload(c, ix, hslot, &X.hslot)) ||
-        (rc = dev_upload(c, ix, kpos, &X.kpos)))
+        (rc = dev_upload(c, ix, rank, &X.rank)) || (rc = dev_upload(c, ix, kt.hslot, &X.hslot)) ||
+        (rc = dev_upload(c, ix, kt.kpos, &X.kpos)))
         return rc;
     X.n = n;
-    X.hbits = hbits;
+    X.hbits = kt.hbits;
     for (int b = 0; b < 4; ++b) X.base_cnt[b] = 0;
     for (int64_t i = 0; i < N; ++i) ++X.base_cnt[T[i]];
     ix->s2 = X;
@@ -378,56 +392,42 @@ int ensure_s2_text(af_ctx *c, af_index *ix) {
     return AF_OK;
 }
 
-// per-context S2 scratch for a batch of n_pairs (chunks of >= chunk_bases bases)
+// a GPeSpec pool for cap_pairs heavy pairs, jobs_per_pair window slots each on average
+int alloc_pe_spec(af_ctx *c, PeSpecBufs &e, int64_t cap_pairs, int64_t jobs_per_pair) {
+    const int64_t cap_jobs = jobs_per_pair * cap_pairs;
+    ALLOCCHK(c, AF_E_HIP, e.cnt.grow(8));
+    ALLOCCHK(c, AF_E_HIP, dev_alloc_all({{e.pair, cap_pairs}, {e.off, cap_pairs}, {e.nj, cap_pairs}, {e.job, cap_jobs},
+                                         {e.res, 4 * AF_G_PE_RES_W * cap_jobs}}));
+    return AF_OK;
+}
+
+// the chunk tables of a batch of n_pairs (chunks of >= chunk_bases bases; at least `floor` chunks) and
+// the insert-size histograms [chunk][orientation][max_ins + 1], zero between calls (K3b clears them)
+int ensure_chunk_stats(af_ctx *c, ChunkStatBufs &b, int64_t n_pairs, int32_t stride, int64_t chunk_bases, int64_t floor,
+                       int32_t max_ins) {
+    const int64_t mc = std::min<int64_t>(n_pairs, 2 * n_pairs * (int64_t)stride / std::max<int64_t>(chunk_bases, 1) + 2) + 1;
+    if (mc > b.max_chunks()) {
+        const int64_t m = std::max(mc, floor);
+        ALLOCCHK(c, AF_E_HIP, dev_alloc_all({{b.pes, 4 * m}, {b.cstart, m + 1}, {b.nchunks, 1}}));
+    }
+    ALLOCCHK(c, AF_E_HIP, b.ghist.grow_zeroed((int64_t)b.max_chunks() * 4 * (max_ins + 1)));
+    return AF_OK;
+}
+
+// per-context S2 scratch for a batch of n_pairs (chunks of >= chunk_bases bases).  The arrays that
+// share the pair capacity go last: s2_plist's size is that capacity only when all of them stand
 int ensure_s2_work(af_ctx *c, int64_t n_pairs, int32_t stride, int64_t chunk_bases, int32_t max_ins) {
-    if (n_pairs > c->s2_cap_pairs) {
-        af_free(c->s2_pool); af_free(c->s2_rmap); af_free(c->s2_plist); af_free(c->s2_scan); af_free(c->s2_plan);
-        c->s2_pool = nullptr; c->s2_rmap = nullptr; c->s2_plist = nullptr; c->s2_scan = nullptr; c->s2_plan = nullptr;
-        c->s2_cap_pairs = 0;
+    if (n_pairs > c->s2_plist.size()) {
         const int64_t cap = std::max<int64_t>(n_pairs, 1 << 16);
+        // K3c's heavy pairs: one in 8 of the batch's pairs, 16 window slots each on average
+        if (int rc = alloc_pe_spec(c, c->s2_sp, std::max<int64_t>(cap / 8, 1024), 16)) return rc;
         // regions: 4 per read (40 B each) -- enough when every read is a candidate with a
         // couple of regions (targeted input); a read past the pool is flagged and counted
-        c->s2_pool_cap = 8 * cap + (1 << 20);
-        HIPCHK(c, hipMalloc(&c->s2_pool, sizeof(S2Reg) * c->s2_pool_cap));
-        HIPCHK(c, hipMalloc(&c->s2_rmap, sizeof(int2) * 2 * cap));
-        HIPCHK(c, hipMalloc(&c->s2_plist, sizeof(int32_t) * cap));
-        HIPCHK(c, hipMalloc(&c->s2_scan, sizeof(int64_t) * cap));
-        HIPCHK(c, hipMalloc(&c->s2_plan, af_s2_plan_bytes() * cap));
-        // K3c's heavy pairs: one in 8 of the batch's pairs, 16 window slots each on average
-        GPeSpec &e = c->s2_sp;
-        af_free(e.pair); af_free(e.off); af_free(e.nj); af_free(e.job); af_free(e.res);
-        e.pair = e.off = e.nj = e.res = nullptr; e.job = nullptr;
-        e.cap_pairs = std::max<int64_t>(cap / 8, 1024); e.cap_jobs = 16 * e.cap_pairs;
-        HIPCHK(c, hipMalloc(&e.pair, sizeof(int32_t) * e.cap_pairs));
-        HIPCHK(c, hipMalloc(&e.off, sizeof(int32_t) * e.cap_pairs));
-        HIPCHK(c, hipMalloc(&e.nj, sizeof(int32_t) * e.cap_pairs));
-        HIPCHK(c, hipMalloc(&e.job, sizeof(int2) * e.cap_jobs));
-        HIPCHK(c, hipMalloc(&e.res, sizeof(int32_t) * 4 * AF_G_PE_RES_W * e.cap_jobs));
-        if (!e.cnt) HIPCHK(c, hipMalloc(&e.cnt, 8 * sizeof(unsigned long long)));
-        c->s2_cap_pairs = cap;
+        ALLOCCHK(c, AF_E_HIP,
+                 dev_alloc_all({{c->s2_pool, 8 * cap + (1 << 20)}, {c->s2_rmap, 2 * cap}, {c->s2_plist, cap},
+                                {c->s2_scan, cap}, {c->s2_plan, (int64_t)af_s2_plan_bytes() * cap}}));
     }
-    const int64_t mc = std::min<int64_t>(n_pairs, 2 * n_pairs * (int64_t)stride / std::max<int64_t>(chunk_bases, 1) + 2) + 1;
-    if (mc > c->s2_max_chunks) {
-        af_free(c->s2_pes); af_free(c->s2_cstart); af_free(c->s2_nchunks);
-        c->s2_pes = nullptr; c->s2_cstart = nullptr; c->s2_nchunks = nullptr;
-        c->s2_max_chunks = 0;
-        const int64_t m = std::max<int64_t>(mc, 64);
-        HIPCHK(c, hipMalloc(&c->s2_pes, sizeof(S2Pes) * 4 * m));
-        HIPCHK(c, hipMalloc(&c->s2_cstart, sizeof(int64_t) * (m + 1)));
-        HIPCHK(c, hipMalloc(&c->s2_nchunks, sizeof(int32_t)));
-        c->s2_max_chunks = (int32_t)m;
-    }
-    // insert-size histograms [chunk][orientation][max_ins + 1], zero between calls (K3b clears them)
-    const int64_t hints = (int64_t)c->s2_max_chunks * 4 * (max_ins + 1);
-    if (hints > c->s2_ghist_ints) {
-        af_free(c->s2_ghist);
-        c->s2_ghist = nullptr;
-        c->s2_ghist_ints = 0;
-        HIPCHK(c, hipMalloc(&c->s2_ghist, sizeof(int32_t) * hints));
-        HIPCHK(c, hipMemset(c->s2_ghist, 0, sizeof(int32_t) * hints));
-        c->s2_ghist_ints = hints;
-    }
-    return AF_OK;
+    return ensure_chunk_stats(c, c->s2_cs, n_pairs, stride, chunk_bases, 64, max_ins);
 }
 
 int check_pe(af_ctx *c, const af_pe *e) {
@@ -437,11 +437,16 @@ int check_pe(af_ctx *c, const af_pe *e) {
     return AF_OK;
 }
 
+// the scoring and occurrence options every align call checks alike
+bool penalties_ok(const af_params *p) {
+    return p->a > 0 && p->b >= 0 && p->o_del >= 0 && p->e_del > 0 && p->o_ins >= 0 && p->e_ins > 0 && p->w >= 0 &&
+           p->max_occ >= 1;
+}
+
 int check_params(af_ctx *c, const af_params *p) {
     if (!p) return fail(c, AF_E_INVALID, "params is NULL");
-    if (p->a <= 0 || p->b < 0 || p->o_del < 0 || p->e_del <= 0 || p->o_ins < 0 || p->e_ins <= 0 || p->w < 0 ||
-        p->min_seed_len < AF_K || p->max_ext < 1 || p->max_ext > 16 || p->max_mems < 1 || p->max_mems > 64 ||
-        p->max_occ < 1)
+    if (!penalties_ok(p) || p->min_seed_len < AF_K || p->max_ext < 1 || p->max_ext > 16 || p->max_mems < 1 ||
+        p->max_mems > 64)
         return fail(c, AF_E_INVALID, "invalid af_params (min_seed_len>=%d, 1<=max_ext<=16, 1<=max_mems<=64)", AF_K);
     return AF_OK;
 }
@@ -449,75 +454,42 @@ int check_params(af_ctx *c, const af_params *p) {
 
 // ---- genome calls (bwa_genome.hip) ------------------------------------------------------
 // per-lane G1 scratch (AF_G1_WPS waves per SIMD) and per-wave G2-G4 scratch (8 waves per CU, <= n_slots of
-// the context's traceback scratch)
+// the context's traceback scratch), each allocated once
 int ensure_genome_scratch(af_ctx *c) {
-    if (c->g1_scr) return AF_OK;
     c->g1_threads = c->n_cu * 4 * AF_G1_WPS * 64;
     c->g2_waves = std::min(c->n_cu * 8, c->n_slots);
-    HIPCHK(c, hipMalloc(&c->g1_scr, af_g1_slot_bytes() * (size_t)c->g1_threads));
-    HIPCHK(c, hipMalloc(&c->g2_scr, af_g2_slot_bytes() * (size_t)c->g2_waves));
+    ALLOCCHK(c, AF_E_HIP, c->g1_scr.grow((int64_t)(af_g1_slot_bytes() * (size_t)c->g1_threads)));
+    ALLOCCHK(c, AF_E_HIP, c->g2_scr.grow((int64_t)(af_g2_slot_bytes() * (size_t)c->g2_waves)));
     // iv fill, G1 next, G1 heavy count / next, G2 first-list count / next
-    HIPCHK(c, hipMalloc(&c->g_iv_fill, 8 * sizeof(unsigned long long)));
-    HIPCHK(c, hipMalloc(&c->g_reg_fill, sizeof(int32_t)));
-    HIPCHK(c, hipMalloc(&c->g_stats, sizeof(int32_t) * AF_GSTAT_N));
-    HIPCHK(c, hipMemset(c->g_stats, 0, sizeof(int32_t) * AF_GSTAT_N));
+    ALLOCCHK(c, AF_E_HIP, c->g_iv_fill.grow(8));
+    ALLOCCHK(c, AF_E_HIP, c->g_reg_fill.grow(1));
+    ALLOCCHK(c, AF_E_HIP, c->g_stats.grow_zeroed(AF_GSTAT_N));
     return ensure_zscratch(c);
 }
 
 // pools for a call over n_reads reads: intervals (96 per read on average; a read's list is at
-// most AF_G_MAX_INTV) and regions (16 per read on average)
+// most AF_G_MAX_INTV) and regions (16 per read on average).  g_iv_off's size is the read capacity
+// of them all: its group goes last
 int ensure_genome_pools(af_ctx *c, int64_t n_reads) {
-    if (n_reads <= c->g_cap_reads) return AF_OK;
+    if (n_reads <= c->g_iv_off.size()) return AF_OK;
     // the region pool's fill and offsets are int32 (at most 16 regions per read on average)
     if (n_reads > INT32_MAX / 16 - AF_G_MAX_REG) return fail(c, AF_E_INVALID, "too many reads for one genome call");
-    af_free(c->g_iv); af_free(c->g_reg); af_free(c->g_iv_off); af_free(c->g_iv_n); af_free(c->g_reg_off);
-    af_free(c->g_reg_n); af_free(c->g1_hv);
-    c->g_iv = nullptr; c->g_reg = nullptr; c->g_iv_off = nullptr; c->g_iv_n = nullptr; c->g_reg_off = nullptr;
-    c->g_reg_n = nullptr; c->g1_hv = nullptr; c->g_cap_reads = 0;
     const int64_t cap = std::max<int64_t>(n_reads, 1 << 14);
-    c->g_iv_cap = cap * 96 + AF_G_MAX_INTV;
-    c->g_reg_cap = cap * 16 + AF_G_MAX_REG;
-    HIPCHK(c, hipMalloc(&c->g_iv, sizeof(GIv) * c->g_iv_cap));
-    HIPCHK(c, hipMalloc(&c->g_reg, sizeof(GReg) * c->g_reg_cap));
-    HIPCHK(c, hipMalloc(&c->g_iv_off, sizeof(int64_t) * cap));
-    HIPCHK(c, hipMalloc(&c->g_iv_n, sizeof(int32_t) * cap));
-    HIPCHK(c, hipMalloc(&c->g_reg_off, sizeof(int32_t) * cap));
-    HIPCHK(c, hipMalloc(&c->g_reg_n, sizeof(int32_t) * cap));
-    HIPCHK(c, hipMalloc(&c->g1_hv, sizeof(int64_t) * cap));
-    // heavy reads: at most every read; 8 pooled chains and 16 seeds per read of the call (a read
-    // that does not fit is extended by its own wave)
-    GHeavy &h = c->g_hv;
-    af_free(h.read); af_free(h.nch); af_free(h.ch_off); af_free(h.sd_off); af_free(h.ch_read);
-    af_free(h.ch); af_free(h.sd); af_free(h.res);
-    h.read = nullptr; h.nch = h.ch_off = h.sd_off = h.ch_read = nullptr; h.ch = h.sd = h.res = nullptr;
-    h.cap_reads = cap; h.cap_ch = std::max<int64_t>(cap * 8, 1 << 16); h.cap_sd = 2 * h.cap_ch;
-    HIPCHK(c, hipMalloc(&h.read, sizeof(int64_t) * h.cap_reads));
-    HIPCHK(c, hipMalloc(&h.nch, sizeof(int32_t) * h.cap_reads));
-    HIPCHK(c, hipMalloc(&h.ch_off, sizeof(int32_t) * h.cap_reads));
-    HIPCHK(c, hipMalloc(&h.sd_off, sizeof(int32_t) * h.cap_reads));
-    HIPCHK(c, hipMalloc(&h.ch_read, sizeof(int32_t) * h.cap_ch));
-    HIPCHK(c, hipMalloc(&h.ch, af_g_chain_bytes() * h.cap_ch));
-    HIPCHK(c, hipMalloc(&h.sd, af_g_seed_bytes() * h.cap_sd));
-    HIPCHK(c, hipMalloc(&h.res, sizeof(GReg) * h.cap_sd));
-    if (!h.cnt) HIPCHK(c, hipMalloc(&h.cnt, 8 * sizeof(unsigned long long)));
     // S4's heavy pairs: up to half the call's pairs (cap counts reads), 8 window slots each on
     // average (a pair that does not fit runs its rescues on its own wave; counted by
     // AF_GSTAT_PE_JOBS: 1,628 of the configs[2] step's 26 k pairs hit the round's first cap of 1/32)
-    GPeSpec &e = c->g_pe;
-    af_free(e.pair); af_free(e.off); af_free(e.nj); af_free(e.job); af_free(e.res);
-    e.pair = e.off = e.nj = e.res = nullptr; e.job = nullptr;
-    e.cap_pairs = std::max<int64_t>(cap / 4, 1024); e.cap_jobs = 8 * e.cap_pairs;
-    HIPCHK(c, hipMalloc(&e.pair, sizeof(int32_t) * e.cap_pairs));
-    HIPCHK(c, hipMalloc(&e.off, sizeof(int32_t) * e.cap_pairs));
-    HIPCHK(c, hipMalloc(&e.nj, sizeof(int32_t) * e.cap_pairs));
-    HIPCHK(c, hipMalloc(&e.job, sizeof(int2) * e.cap_jobs));
-    HIPCHK(c, hipMalloc(&e.res, sizeof(int32_t) * 4 * AF_G_PE_RES_W * e.cap_jobs));
-    if (!e.cnt) HIPCHK(c, hipMalloc(&e.cnt, 8 * sizeof(unsigned long long)));
-    af_free(c->g2_list); af_free(c->g2_flag);
-    c->g2_list = nullptr; c->g2_flag = nullptr;
-    HIPCHK(c, hipMalloc(&c->g2_list, sizeof(int32_t) * cap));
-    HIPCHK(c, hipMalloc(&c->g2_flag, cap));
-    c->g_cap_reads = cap;
+    if (int rc = alloc_pe_spec(c, c->g_pe, std::max<int64_t>(cap / 4, 1024), 8)) return rc;
+    // heavy reads: at most every read; 8 pooled chains and 16 seeds per read of the call (a read
+    // that does not fit is extended by its own wave)
+    const int64_t cap_ch = std::max<int64_t>(cap * 8, 1 << 16), cap_sd = 2 * cap_ch;
+    ALLOCCHK(c, AF_E_HIP, c->hv_cnt.grow(8));
+    ALLOCCHK(c, AF_E_HIP,
+             dev_alloc_all({{c->hv_read, cap}, {c->hv_nch, cap}, {c->hv_ch_off, cap}, {c->hv_sd_off, cap},
+                            {c->hv_ch_read, cap_ch}, {c->hv_ch, (int64_t)af_g_chain_bytes() * cap_ch},
+                            {c->hv_sd, (int64_t)af_g_seed_bytes() * cap_sd}, {c->hv_res, cap_sd},
+                            {c->g2_list, cap}, {c->g2_flag, cap}, {c->g1_hv, cap},
+                            {c->g_iv, cap * 96 + AF_G_MAX_INTV}, {c->g_reg, cap * 16 + AF_G_MAX_REG},
+                            {c->g_iv_n, cap}, {c->g_reg_off, cap}, {c->g_reg_n, cap}, {c->g_iv_off, cap}}));
     return AF_OK;
 }
 
@@ -530,8 +502,8 @@ int ensure_genome_pools(af_ctx *c, int64_t n_reads) {
 // 203 ms)
 GWork genome_work(af_ctx *c, int64_t n_reads) {
     GWork w;
-    w.iv = c->g_iv; w.iv_cap = c->g_iv_cap; w.iv_fill = c->g_iv_fill; w.iv_off = c->g_iv_off; w.iv_n = c->g_iv_n;
-    w.reg = c->g_reg; w.reg_cap = c->g_reg_cap; w.reg_fill = c->g_reg_fill; w.reg_off = c->g_reg_off;
+    w.iv = c->g_iv; w.iv_cap = c->g_iv.size(); w.iv_fill = c->g_iv_fill; w.iv_off = c->g_iv_off; w.iv_n = c->g_iv_n;
+    w.reg = c->g_reg; w.reg_cap = c->g_reg.size(); w.reg_fill = c->g_reg_fill; w.reg_off = c->g_reg_off;
     w.reg_n = c->g_reg_n;
     w.heads = c->ctrl + AF_CTRL_G_HEADS;
     w.g1_next = c->g_iv_fill + 1;
@@ -542,10 +514,12 @@ GWork genome_work(af_ctx *c, int64_t n_reads) {
         mx = per_cu >= 160 ? mx : per_cu >= 96 ? std::min(mx, 1024) : 1;
     }
     w.g1_max_ext = c->g1_hv ? mx : 0;
-    w.hv = c->g_hv;
-    w.hv.min_chains = c->g_hv.cnt ? c->g_heavy_min : 0;
-    w.pe = c->g_pe;
-    w.pe.min_windows = c->g_pe.cnt ? c->g_pe_min : 0;
+    w.hv.read = c->hv_read; w.hv.nch = c->hv_nch; w.hv.ch_off = c->hv_ch_off; w.hv.sd_off = c->hv_sd_off;
+    w.hv.ch_read = c->hv_ch_read; w.hv.ch = c->hv_ch.get(); w.hv.sd = c->hv_sd.get(); w.hv.res = c->hv_res.get();
+    w.hv.cnt = c->hv_cnt;
+    w.hv.cap_reads = c->hv_read.size(); w.hv.cap_ch = c->hv_ch_read.size(); w.hv.cap_sd = c->hv_res.size();
+    w.hv.min_chains = c->hv_cnt ? c->g_heavy_min : 0;
+    w.pe = c->g_pe.view(c->g_pe_min);
     w.g2_list = c->g2_list; w.g2_flag = c->g2_flag; w.g2_list_n = c->g_iv_fill + 4; w.g2_list_next = c->g_iv_fill + 5;
     w.g2_first_occ = c->g2_flag ? c->g2_first_occ : 0;
     if (const char *ca = getenv("AF_G_CHAIN_ARR")) w.chain_arr = std::max(0, std::min(AF_G_ARR, atoi(ca)));  // read per call
@@ -553,42 +527,24 @@ GWork genome_work(af_ctx *c, int64_t n_reads) {
     return w;
 }
 
+// S2Work view of the S4 chunk statistics (k_s2_pestat; ragged chunk starts from the lengths)
+S2Work genome_pe_work(const af_ctx *c) {
+    S2Work sw{};
+    sw.ghist = c->g_cs.ghist; sw.pes = c->g_cs.pes; sw.ppc = 0; sw.cstart = c->g_cs.cstart; sw.n_chunks = c->g_cs.nchunks;
+    sw.max_chunks = c->g_cs.max_chunks();
+    return sw;
+}
+
 int check_genome_call(af_ctx *c, const af_genome *g, const af_params *p, const af_pe *e, int32_t stride) {
     if (!c || !g || !g->dev.sa) return fail(c, AF_E_INVALID, "null context or genome");
-    if (!p || p->a <= 0 || p->b < 0 || p->o_del < 0 || p->e_del <= 0 || p->o_ins < 0 || p->e_ins <= 0 || p->w < 0 ||
-        p->min_seed_len < 1 || p->max_occ < 1)
-        return fail(c, AF_E_INVALID, "invalid af_params");
+    if (!p || !penalties_ok(p) || p->min_seed_len < 1) return fail(c, AF_E_INVALID, "invalid af_params");
     if (stride < 1) return fail(c, AF_E_INVALID, "stride must be >= 1");
     return e ? check_pe(c, e) : AF_OK;
 }
 
-// S2Work view of the S4 chunk statistics (k_s2_pestat; ragged chunk starts from the lengths)
 int ensure_genome_pe(af_ctx *c, int64_t n_pairs, int32_t stride, int64_t chunk_bases, int32_t max_ins) {
-    const int64_t mc = std::min<int64_t>(n_pairs, 2 * n_pairs * (int64_t)stride / std::max<int64_t>(chunk_bases, 1) + 2) + 1;
-    if (mc > c->g_max_chunks) {
-        af_free(c->g_pes); af_free(c->g_cstart); af_free(c->g_nchunks);
-        c->g_pes = nullptr; c->g_cstart = nullptr; c->g_nchunks = nullptr; c->g_max_chunks = 0;
-        const int64_t m = std::max<int64_t>(mc, 16);
-        HIPCHK(c, hipMalloc(&c->g_pes, sizeof(S2Pes) * 4 * m));
-        HIPCHK(c, hipMalloc(&c->g_cstart, sizeof(int64_t) * (m + 1)));
-        HIPCHK(c, hipMalloc(&c->g_nchunks, sizeof(int32_t)));
-        c->g_max_chunks = (int32_t)m;
-    }
-    if (n_pairs > c->g_scan_cap) {
-        af_free(c->g_scan);
-        c->g_scan = nullptr; c->g_scan_cap = 0;
-        HIPCHK(c, hipMalloc(&c->g_scan, sizeof(int64_t) * std::max<int64_t>(n_pairs, 1)));
-        c->g_scan_cap = std::max<int64_t>(n_pairs, 1);
-    }
-    const int64_t hints = (int64_t)c->g_max_chunks * 4 * (max_ins + 1);
-    if (hints > c->g_ghist_ints) {
-        af_free(c->g_ghist);
-        c->g_ghist = nullptr; c->g_ghist_ints = 0;
-        HIPCHK(c, hipMalloc(&c->g_ghist, sizeof(int32_t) * hints));
-        HIPCHK(c, hipMemset(c->g_ghist, 0, sizeof(int32_t) * hints));
-        c->g_ghist_ints = hints;
-    }
-    return AF_OK;
+    ALLOCCHK(c, AF_E_HIP, c->g_scan.grow(std::max<int64_t>(n_pairs, 1)));
+    return ensure_chunk_stats(c, c->g_cs, n_pairs, stride, chunk_bases, 16, max_ins);
 }
 
 int genome_build(af_ctx *c, const char *blob, int64_t n_blob, const int64_t *ctg_off, const int64_t *ctg_len,
@@ -601,20 +557,18 @@ int genome_build(af_ctx *c, const char *blob, int64_t n_blob, const int64_t *ctg
             return fail(c, AF_E_INVALID, "contig %d outside the blob", k);
     (void)hipSetDevice(c->device);
     const uint8_t *d_blob = reinterpret_cast<const uint8_t *>(blob);
-    uint8_t *tmp = nullptr;
+    DevBuf<uint8_t> tmp;
     if (!on_device) {
-        HIPCHK(c, hipMalloc(&tmp, n_blob));
-        if (hipMemcpy(tmp, blob, n_blob, hipMemcpyHostToDevice) != hipSuccess) {
-            af_free(tmp);
+        ALLOCCHK(c, AF_E_HIP, tmp.alloc(n_blob));
+        if (hipMemcpy(tmp, blob, n_blob, hipMemcpyHostToDevice) != hipSuccess)
             return fail(c, AF_E_HIP, "genome copy to the device failed");
-        }
         d_blob = tmp;
     }
     af_genome *g = new (std::nothrow) af_genome;
-    if (!g) { af_free(tmp); return fail(c, AF_E_NOMEM, "out of host memory"); }
+    if (!g) return fail(c, AF_E_NOMEM, "out of host memory");
     g->ctx = c;
     const hipError_t e = af_fm_build(d_blob, ctg_off, ctg_len, n_ctg, &g->dev, c->stream);
-    af_free(tmp);
+    tmp.reset();
     if (e != hipSuccess) {
         delete g;
         return fail(c, e == hipErrorOutOfMemory ? AF_E_NOMEM : AF_E_HIP, "genome index build: %s", hipGetErrorString(e));
@@ -665,10 +619,8 @@ int af_ctx_create(int device, af_ctx **out) {
         c->g1_max_ext = std::max(0, atoi(hv));
         c->g1_ext_env = true;
     }
-    if (hipMalloc(&c->ctrl, AF_CTRL_BYTES) != hipSuccess) { delete c; return AF_E_HIP; }
-    if (hipMemset(c->ctrl, 0, AF_CTRL_BYTES) != hipSuccess) { af_free(c->ctrl); delete c; return AF_E_HIP; }
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        af_free(c->ctrl);
+    if (c->ctrl.grow_zeroed(AF_CTRL_BYTES / sizeof(int32_t)) != hipSuccess ||
+        hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return AF_E_HIP;
     }
@@ -679,34 +631,9 @@ int af_ctx_create(int device, af_ctx **out) {
 void af_ctx_destroy(af_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    af_free(c->ctrl); af_free(c->cand); af_free(c->zscratch); af_free(c->bscratch); af_free(c->blat_caps); af_free(c->blat_ord_work); af_free(c->blat_order); af_free(c->blat_stage); af_free(c->blat_stage_n); af_free(c->d_packed);
-    af_free(c->d_reads); af_free(c->d_lens);
-    af_free(c->d_flag); af_free(c->d_pos); af_free(c->d_score); af_free(c->d_ncig); af_free(c->d_hits);
-    af_free(c->d_cigar);
-    af_free(c->s2_pool); af_free(c->s2_rmap); af_free(c->s2_plist); af_free(c->s2_ghist); af_free(c->s2_scan);
-    af_free(c->s2_plan);
-    af_free(c->s2_pes); af_free(c->s2_cstart); af_free(c->s2_nchunks);
-    af_free(c->s3_keys); af_free(c->s3_temp); af_free(c->s3_counts);
-    af_free(c->g_sel); af_free(c->g_sel_n); af_free(c->g_temp);
-    af_free(c->g2_scr_pe); af_free(c->zscratch_pe);
-    af_free(c->g_hv.read); af_free(c->g_hv.nch); af_free(c->g_hv.ch_off); af_free(c->g_hv.sd_off); af_free(c->g_hv.ch_read);
-    af_free(c->g_hv.ch); af_free(c->g_hv.sd); af_free(c->g_hv.res); af_free(c->g_hv.cnt);
-    af_free(c->g_pe.pair); af_free(c->g_pe.off); af_free(c->g_pe.nj); af_free(c->g_pe.job); af_free(c->g_pe.res);
-    af_free(c->g_pe.cnt);
-    af_free(c->s2_sp.pair); af_free(c->s2_sp.off); af_free(c->s2_sp.nj); af_free(c->s2_sp.job); af_free(c->s2_sp.res);
-    af_free(c->s2_sp.cnt);
-    af_free(c->g2_list); af_free(c->g2_flag);
     if (c->g_ev) (void)hipEventDestroy(c->g_ev);
-    af_free(c->g1_scr); af_free(c->g2_scr); af_free(c->g_iv); af_free(c->g_reg); af_free(c->g_iv_fill);
-    af_free(c->g_reg_fill); af_free(c->g_stats); af_free(c->g_iv_n); af_free(c->g_reg_off); af_free(c->g_reg_n); af_free(c->g1_hv);
-    af_free(c->g_iv_off); af_free(c->g_ghist); af_free(c->g_nchunks); af_free(c->g_cstart); af_free(c->g_scan);
-    af_free(c->g_pes); af_free(c->g_recs); af_free(c->g_nrec); af_free(c->g_hlens); af_free(c->g_hreads);
-    af_free(c->s5_keep); af_free(c->s5_sel); af_free(c->s5_nsel); af_free(c->s5_temp);
-    af_free(c->s6_flag); af_free(c->s6_idx); af_free(c->s6_sflag); af_free(c->s6_sidx); af_free(c->s6_temp);
-    af_free(c->blat_hv.strands);
-    af_free(c->blat_hv.ctrl);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // the DevBuf members free the device memory
 }
 
 const char *af_last_error(const af_ctx *c) { return c ? c->err.c_str() : "null context"; }
@@ -729,38 +656,13 @@ int af_index_build(af_ctx *c, const char *anchor, int64_t len, af_index **out) {
         D2[i >> 4] |= (uint32_t)(D[i] & 3) << (2 * (i & 15));
         if (D[i] > 3) Dn[i >> 5] |= 1u << (i & 31);
     }
-    // 16-mer occurrences that do not cross the strand boundary, sorted by (kmer, pos)
-    std::vector<uint64_t> occ;
-    occ.reserve(n2);
-    for (int64_t p = 0; p + AF_K <= n2; ++p) {
-        if (p < n && p + AF_K > n) continue;
-        uint32_t k = 0;
-        bool ok = true;
-        for (int u = 0; u < AF_K && ok; ++u) {
-            ok = D[p + u] < 4;
-            k |= (uint32_t)(D[p + u] & 3) << (2 * u);
-        }
-        if (ok) occ.push_back((uint64_t)k << 32 | (uint64_t)p);
-    }
-    std::sort(occ.begin(), occ.end());
-    std::vector<uint32_t> keys;
-    std::vector<int32_t> starts, cnts, kpos(occ.size());
-    for (size_t i = 0; i < occ.size(); ++i) {
-        const uint32_t k = (uint32_t)(occ[i] >> 32);
-        kpos[i] = (int32_t)(occ[i] & 0xffffffffu);
-        if (i == 0 || k != keys.back()) { keys.push_back(k); starts.push_back((int32_t)i); cnts.push_back(0); }
-        ++cnts.back();
-    }
-    const int64_t nd = (int64_t)keys.size();
-    int hbits = 10;
-    while ((1LL << hbits) < 2 * nd) ++hbits;
-    const uint32_t hm = (1u << hbits) - 1u;
-    std::vector<int4> hslot(1u << hbits, int4{0, 0, 0, 0});
-    for (int64_t i = 0; i < nd; ++i) {
-        uint32_t s = af_fmix(keys[i]) & hm;
-        while (hslot[s].z) s = (s + 1) & hm;
-        hslot[s] = int4{(int)keys[i], starts[i], cnts[i], kpos[starts[i]]};
-    }
+    // the 16-mers that do not cross the strand boundary and hold no N
+    const KmerTable kt = kmer_table(D, [&](int64_t p) {
+        if (p < n && p + AF_K > n) return true;
+        for (int u = 0; u < AF_K; ++u)
+            if (D[p + u] > 3) return true;
+        return false;
+    });
     // Bloom filter of the distinct 16-mers of the bwa text that do not cross the strand boundary
     // (K1; S2 seeds never cross it): 2^bl_bits 32-bit words, ~2.4 words per key (at most 2^15
     // words = 128 KiB, a 6.8 kb anchor), four bits in each of two words
@@ -793,14 +695,14 @@ int af_index_build(af_ctx *c, const char *anchor, int64_t len, af_index **out) {
     int rc = AF_OK;
     const uint32_t *bld = nullptr;
     if ((rc = dev_upload(c, ix, D, &ix->dev.D)) || (rc = dev_upload(c, ix, D2, &ix->dev.D2)) ||
-        (rc = dev_upload(c, ix, Dn, &ix->dev.Dn)) || (rc = dev_upload(c, ix, hslot, &ix->dev.hslot)) ||
-        (rc = dev_upload(c, ix, kpos, &ix->dev.kpos)) || (rc = dev_upload(c, ix, bloom, &bld))) {
+        (rc = dev_upload(c, ix, Dn, &ix->dev.Dn)) || (rc = dev_upload(c, ix, kt.hslot, &ix->dev.hslot)) ||
+        (rc = dev_upload(c, ix, kt.kpos, &ix->dev.kpos)) || (rc = dev_upload(c, ix, bloom, &bld))) {
         af_index_free(ix);
         return rc;
     }
     ix->dev.bloom = bld;
     ix->dev.n = n;
-    ix->dev.hbits = hbits;
+    ix->dev.hbits = kt.hbits;
     ix->dev.bl_bits = bl_bits;
     *out = ix;
     return AF_OK;
@@ -809,8 +711,7 @@ int af_index_build(af_ctx *c, const char *anchor, int64_t len, af_index **out) {
 void af_index_free(af_index *ix) {
     if (!ix) return;
     if (ix->ctx) (void)hipSetDevice(ix->ctx->device);
-    for (int i = 0; i < ix->n_allocs; ++i) af_free(ix->allocs[i]);
-    delete ix;
+    delete ix;  // frees the owned device arrays
 }
 
 int64_t af_index_anchor_len(const af_index *ix) { return ix ? ix->dev.n : -1; }
@@ -912,7 +813,7 @@ static int align_candidates(af_ctx *c, af_index *ix, const uint8_t *d_reads, int
         return fail(c, AF_E_INVALID, "output arrays must all be non-NULL");
     if ((((uintptr_t)o->flag | (uintptr_t)o->pos | (uintptr_t)o->score | (uintptr_t)o->n_cigar) & 7) != 0)
         return fail(c, AF_E_INVALID, "flag/pos/score/n_cigar arrays must be 8-byte aligned");
-    if (2 * n_pairs > c->cap_reads) return fail(c, AF_E_INVALID, "seed filter was not run for this batch");
+    if (2 * n_pairs > c->cand.size()) return fail(c, AF_E_INVALID, "seed filter was not run for this batch");
     (void)hipSetDevice(c->device);
     if ((rc = ensure_zscratch(c))) return rc;
     if ((rc = ensure_s2_text(c, ix))) return rc;
@@ -922,25 +823,24 @@ static int align_candidates(af_ctx *c, af_index *ix, const uint8_t *d_reads, int
     const int slot = (int)((c->epoch - 1) & 1);
     int32_t *n_cand = c->ctrl + AF_HEAD_STRIDE * slot;
     S2Work w{};
-    w.pool = c->s2_pool; w.pool_cap = c->s2_pool_cap;
+    w.pool = c->s2_pool; w.pool_cap = c->s2_pool.size();
     w.pool_n = c->ctrl + AF_CTRL_S2_POOL + AF_HEAD_STRIDE * slot;
     w.rmap = c->s2_rmap;
     w.plist = c->s2_plist;
     w.n_plist = c->ctrl + AF_CTRL_S2_NPAIRS + AF_HEAD_STRIDE * slot;
-    w.ghist = c->s2_ghist; w.pes = c->s2_pes;
-    w.cstart = c->s2_cstart; w.n_chunks = c->s2_nchunks; w.max_chunks = c->s2_max_chunks;
+    w.ghist = c->s2_cs.ghist; w.pes = c->s2_cs.pes;
+    w.cstart = c->s2_cs.cstart; w.n_chunks = c->s2_cs.nchunks; w.max_chunks = c->s2_cs.max_chunks();
     if (!d_lens) {  // every read has length stride: pairs per chunk is arithmetic (bseq_read)
         w.ppc = (pe.chunk_bases + 2 * (int64_t)stride - 1) / (2 * (int64_t)stride);
         w.n_chunks_u = (int32_t)((n_pairs + w.ppc - 1) / w.ppc);
     }
     w.heads_k2 = c->ctrl + AF_CTRL_HEADS2; w.heads_k3 = c->ctrl + AF_CTRL_S2_HEADS3;
-    w.plan = c->s2_plan;
-    w.sp = c->s2_sp;
-    w.sp.min_windows = c->s2_sp.cnt ? c->s2_sp_min : 0;
+    w.plan = c->s2_plan.get();
+    w.sp = c->s2_sp.view(c->s2_sp_min);
     S2Opt opt{pe.pen_unpaired, pe.max_ins, pe.max_matesw, pe.split_width, pe.max_mem_intv, pe.max_chain_gap, pe.pair_base};
     if (d_lens)
-        HIPCHK(c, af_launch_s2_chunks(n_pairs, stride, d_lens, pe.chunk_bases, c->s2_cstart, c->s2_scan,
-                                      c->s2_max_chunks, c->s2_nchunks, s));
+        HIPCHK(c, af_launch_s2_chunks(n_pairs, stride, d_lens, pe.chunk_bases, c->s2_cs.cstart, c->s2_scan,
+                                      c->s2_cs.max_chunks(), c->s2_cs.nchunks, s));
     if (tails && !append) HIPCHK(c, hipMemsetAsync(tails->n_tails, 0, 4, s));
     HIPCHK(c, af_launch_s2(ix->s2, d_reads, n_pairs, stride, d_lens, *p, opt, o->hits, c->cand, n_cand, w, *o,
                            c->zscratch, c->n_slots, c->n_cu, tails, s));
@@ -956,23 +856,12 @@ int af_align_pairs(af_ctx *c, const af_index *ix, const uint8_t *reads, int64_t 
     (void)hipSetDevice(c->device);
     const int64_t nr = 2 * n_pairs;
     const int64_t bytes = nr * (int64_t)stride;
-    if (bytes > c->cap_bytes) {
-        af_free(c->d_reads); af_free(c->d_lens);
-        c->d_reads = nullptr; c->d_lens = nullptr; c->cap_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->d_reads, bytes + 64));
-        HIPCHK(c, hipMalloc(&c->d_lens, sizeof(int32_t) * nr + 64));
-        c->cap_bytes = bytes;
-    }
-    if (nr > c->cap_out) {
-        af_free(c->d_flag); af_free(c->d_pos); af_free(c->d_score); af_free(c->d_ncig); af_free(c->d_hits);
-        af_free(c->d_cigar);
-        c->cap_out = 0;
-        HIPCHK(c, hipMalloc(&c->d_flag, 4 * nr)); HIPCHK(c, hipMalloc(&c->d_pos, 4 * nr));
-        HIPCHK(c, hipMalloc(&c->d_score, 4 * nr)); HIPCHK(c, hipMalloc(&c->d_ncig, 4 * nr));
-        HIPCHK(c, hipMalloc(&c->d_hits, 4 * nr));
-        HIPCHK(c, hipMalloc(&c->d_cigar, sizeof(uint32_t) * AF_MAX_CIGAR * nr));
-        c->cap_out = nr;
-    }
+    // staging (padded for the kernels' wide loads) and the six output arrays, each grown on its own
+    ALLOCCHK(c, AF_E_HIP, c->d_reads.grow(bytes + 64));
+    ALLOCCHK(c, AF_E_HIP, c->d_lens.grow(nr + 16));
+    if (nr > c->d_flag.size())
+        ALLOCCHK(c, AF_E_HIP, dev_alloc_all({{c->d_pos, nr}, {c->d_score, nr}, {c->d_ncig, nr}, {c->d_hits, nr},
+                                             {c->d_cigar, AF_MAX_CIGAR * nr}, {c->d_flag, nr}}));
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(c->d_reads, reads, bytes, hipMemcpyHostToDevice, s));
     if (lens) {
@@ -981,7 +870,7 @@ int af_align_pairs(af_ctx *c, const af_index *ix, const uint8_t *reads, int64_t 
         HIPCHK(c, hipMemcpyAsync(c->d_lens, lens, 4 * nr, hipMemcpyHostToDevice, s));
     }
     af_aln_out d{c->d_flag, c->d_pos, c->d_score, c->d_ncig, c->d_hits, c->d_cigar};
-    int rc = af_align_pairs_device(c, ix, c->d_reads, n_pairs, stride, lens ? c->d_lens : nullptr, p, pe, &d, s);
+    int rc = af_align_pairs_device(c, ix, c->d_reads, n_pairs, stride, lens ? c->d_lens.get() : nullptr, p, pe, &d, s);
     if (rc) return rc;
     if (out->flag) HIPCHK(c, hipMemcpyAsync(out->flag, c->d_flag, 4 * nr, hipMemcpyDeviceToHost, s));
     if (out->pos) HIPCHK(c, hipMemcpyAsync(out->pos, c->d_pos, 4 * nr, hipMemcpyDeviceToHost, s));
@@ -997,13 +886,9 @@ int af_align_pairs(af_ctx *c, const af_index *ix, const uint8_t *reads, int64_t 
         HIPCHK(c, hipMemcpy(&np, c->ctrl + AF_CTRL_S2_NPAIRS + AF_HEAD_STRIDE * slot, sizeof np, hipMemcpyDeviceToHost));
         if (np > 0) {
             const int64_t nrows = 2 * (int64_t)np;
-            if (nrows > c->cap_packed) {
-                af_free(c->d_packed); c->d_packed = nullptr; c->cap_packed = 0;
-                HIPCHK(c, hipMalloc(&c->d_packed, sizeof(uint32_t) * AF_MAX_CIGAR * (size_t)nrows));
-                c->cap_packed = nrows;
-            }
+            ALLOCCHK(c, AF_E_HIP, c->d_packed.grow(AF_MAX_CIGAR * nrows));
             hipLaunchKernelGGL(k_gather_cigar, dim3((unsigned)std::min<int64_t>(4096, (nrows * 8 + 255) / 256)),
-                               dim3(256), 0, s, c->s2_plist, nrows, c->d_cigar, c->d_packed);
+                               dim3(256), 0, s, c->s2_plist.get(), nrows, c->d_cigar.get(), c->d_packed.get());
             HIPCHK(c, hipGetLastError());
             std::vector<int32_t> ids((size_t)np);
             std::vector<uint32_t> rows((size_t)nrows * AF_MAX_CIGAR);
@@ -1031,21 +916,14 @@ int af_partition_device(af_ctx *c, const int32_t *d_flag, const int32_t *d_pos, 
         HIPCHK(c, hipMemsetAsync(d_counts, 0, 3 * sizeof(int64_t), s));
         return AF_OK;
     }
-    if (n_reads > c->s3_cap) {
+    if (2 * n_reads > c->s3_keys.size()) {
         HIPCHK(c, hipStreamSynchronize(s));
-        if (c->s3_keys) (void)hipFree(c->s3_keys);
-        if (c->s3_temp) (void)hipFree(c->s3_temp);
-        c->s3_keys = nullptr; c->s3_temp = nullptr; c->s3_cap = 0;
         const size_t tb = af_s3_temp_bytes(n_reads);
-        if (hipMalloc(&c->s3_keys, 2 * sizeof(uint64_t) * (size_t)n_reads) != hipSuccess ||
-            hipMalloc(&c->s3_temp, tb) != hipSuccess)
-            return fail(c, AF_E_NOMEM, "S3 scratch for %lld reads", (long long)n_reads);
-        c->s3_cap = n_reads;
+        ALLOCCHK(c, AF_E_NOMEM, dev_alloc_all({{c->s3_keys, 2 * n_reads}, {c->s3_temp, (int64_t)tb}}));
         c->s3_temp_bytes = tb;
     }
-    if (!c->s3_counts && hipMalloc(&c->s3_counts, 4 * sizeof(int64_t)) != hipSuccess)
-        return fail(c, AF_E_NOMEM, "S3 counts");
-    HIPCHK(c, af_launch_s3(d_flag, d_pos, n_reads, ref_len, c->s3_keys, c->s3_keys + c->s3_cap, c->s3_temp,
+    ALLOCCHK(c, AF_E_NOMEM, c->s3_counts.grow(4));
+    HIPCHK(c, af_launch_s3(d_flag, d_pos, n_reads, ref_len, c->s3_keys, c->s3_keys + c->s3_keys.size() / 2, c->s3_temp,
                            c->s3_temp_bytes, c->s3_counts, d_tmp1, d_tmp2, d_anchored, s));
     HIPCHK(c, hipMemcpyAsync(d_counts, c->s3_counts, 3 * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     return AF_OK;
@@ -1084,16 +962,12 @@ int af_gather_reads_device(af_ctx *c, const uint8_t *d_reads, int32_t stride, co
         return fail(c, AF_E_INVALID, "af_gather_reads_device: null buffer");
     (void)hipSetDevice(c->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (mode == AF_GATHER_SPLIT_SAM && n_rows > c->g_cap) {
-        af_free(c->g_sel); af_free(c->g_temp);
-        c->g_sel = nullptr; c->g_temp = nullptr; c->g_cap = 0;
+    if (mode == AF_GATHER_SPLIT_SAM && n_rows > c->g_sel.size()) {
         const size_t tb = af_gather_temp_bytes(n_rows);
-        HIPCHK(c, hipMalloc(&c->g_sel, sizeof(int32_t) * (size_t)n_rows));
-        HIPCHK(c, hipMalloc(&c->g_temp, std::max<size_t>(tb, 16)));
-        c->g_cap = n_rows;
+        ALLOCCHK(c, AF_E_HIP, dev_alloc_all({{c->g_temp, (int64_t)std::max<size_t>(tb, 16)}, {c->g_sel, n_rows}}));
         c->g_temp_bytes = tb;
     }
-    if (mode == AF_GATHER_SPLIT_SAM && !c->g_sel_n) HIPCHK(c, hipMalloc(&c->g_sel_n, sizeof(int64_t)));
+    if (mode == AF_GATHER_SPLIT_SAM) ALLOCCHK(c, AF_E_HIP, c->g_sel_n.grow(1));
     af_aln_out none{};
     HIPCHK(c, af_launch_gather(d_reads, stride, d_lens, d_rows, n_rows, mode, d_out ? *d_out : none, first, step, cap,
                                d_q, d_q_lens, d_q_rows, d_n_q, c->g_sel, c->g_sel_n, c->g_temp, c->g_temp_bytes, s));
@@ -1119,19 +993,18 @@ static int tile_build(af_ctx *c, const char *seq, int64_t len, int32_t step, af_
     ix->ctx = c;
     ix->is_tile = true;
     const uint8_t *d = reinterpret_cast<const uint8_t *>(seq);
-    void *tmp = nullptr;
+    DevBuf<uint8_t> tmp;
     hipError_t e = hipSuccess;
     if (!dev) {
-        if ((e = hipMalloc(&tmp, (size_t)len)) != hipSuccess ||
+        if ((e = tmp.alloc(len)) != hipSuccess ||
             (e = hipMemcpyAsync(tmp, seq, (size_t)len, hipMemcpyHostToDevice, c->stream)) != hipSuccess) {
-            af_free(tmp);
             af_index_free(ix);
             return fail(c, AF_E_HIP, "af_tile_index_build: upload: %s", hipGetErrorString(e));
         }
-        d = static_cast<const uint8_t *>(tmp);
+        d = tmp;
     }
-    e = af_build_tile_index(d, len, step, &ix->tile, ix->allocs, &ix->n_allocs, c->stream);
-    af_free(tmp);
+    e = af_build_tile_index(d, len, step, &ix->tile, ix->owned, c->stream);
+    tmp.reset();
     if (e != hipSuccess) {
         af_index_free(ix);
         return fail(c, AF_E_HIP, "af_tile_index_build: %s", hipGetErrorString(e));
@@ -1163,19 +1036,20 @@ static int check_blat(af_ctx *c, const af_index *ix, const af_blat_params *p, in
     return AF_OK;
 }
 
-// a search's launch arguments on c's scratch; heavy strands are deferred to c->blat_hv's table
+// a search's launch arguments on c's scratch; heavy strands are deferred to the blat_hv_* table
 static BlatLaunch blat_launch(af_ctx *c, const af_index *ix, const uint8_t *q, const int32_t *n_q, const int32_t *first,
                               int64_t cap, int32_t stride, const int32_t *lens, const af_blat_params &p, af_psl *rows,
                               int32_t *n_rows, int32_t max_rows, const int32_t *order, bool with_spill) {
     BlatLaunch B;
     B.X = ix->tile;
     B.queries = q; B.n_queries = n_q; B.q_first = first; B.cap = cap; B.stride = stride; B.lens = lens; B.p = p;
-    B.heads = c->ctrl + AF_CTRL_PLACE_HEADS; B.bscratch = c->bscratch; B.n_slots = c->blat_slots;
+    B.heads = c->ctrl + AF_CTRL_PLACE_HEADS; B.bscratch = c->bscratch;
+    B.n_slots = (int32_t)(c->bscratch.size() / (int64_t)AF_BLAT_SLOT_BYTES);
     B.rows = rows; B.n_rows = n_rows; B.max_rows = max_rows; B.order = order;
     B.stage = c->blat_stage; B.stage_n = c->blat_stage_n;
     B.caps = BlatCaps{c->blat_caps, with_spill ? c->blat_qcaps : nullptr, with_spill ? c->blat_qcap : 0};
     if (with_spill) B.spill = c->blat_spill;
-    B.hv = c->blat_hv;
+    B.hv = blat_heavy(c);
     return B;
 }
 
@@ -1195,16 +1069,10 @@ int af_blat(af_ctx *c, const af_index *ix, const uint8_t *queries, int64_t n_que
         (rc = ensure_blat_stage(c, n_queries, max_rows)) || (rc = ensure_blat_heavy(c, n_queries)))
         return rc;
     const int64_t bytes = n_queries * (int64_t)stride, nr = n_queries * (int64_t)max_rows;
-    uint8_t *d_q = nullptr;
-    int32_t *d_lens = nullptr, *d_nrows = nullptr;
-    af_psl *d_rows = nullptr;
-    auto done = [&](int code) {
-        af_free(d_q); af_free(d_lens); af_free(d_nrows); af_free(d_rows);
-        return code;
-    };
-    if (hipMalloc(&d_q, bytes + 64) != hipSuccess || hipMalloc(&d_lens, 4 * n_queries + 64) != hipSuccess ||
-        hipMalloc(&d_nrows, 4 * n_queries + 64) != hipSuccess || hipMalloc(&d_rows, sizeof(af_psl) * nr) != hipSuccess)
-        return done(fail(c, AF_E_NOMEM, "af_blat: device buffers"));
+    DevBuf<uint8_t> d_q;
+    DevBuf<int32_t> d_lens, d_nrows;
+    DevBuf<af_psl> d_rows;
+    ALLOCCHK(c, AF_E_NOMEM, dev_alloc_all({{d_q, bytes + 64}, {d_lens, n_queries + 16}, {d_nrows, n_queries + 16}, {d_rows, nr}}));
     hipStream_t s = c->stream;
     const int32_t nq = (int32_t)n_queries;
     hipError_t e;
@@ -1215,16 +1083,16 @@ int af_blat(af_ctx *c, const af_index *ix, const uint8_t *queries, int64_t n_que
         // rows past a query's n_rows come back zeroed, not as stale device memory
         (e = hipMemsetAsync(d_rows, 0, sizeof(af_psl) * nr, s)) != hipSuccess ||
         (e = af_launch_blat_order(ix->tile, d_q, c->ctrl + AF_CTRL_PLACE_N, n_queries, stride,
-                                  lens ? d_lens : nullptr, p->rep_match, c->blat_ord_work, c->blat_order, s)) !=
+                                  lens ? d_lens.get() : nullptr, p->rep_match, c->blat_ord_work, c->blat_order, s)) !=
             hipSuccess ||
         (e = af_launch_blat(blat_launch(c, ix, d_q, c->ctrl + AF_CTRL_PLACE_N, nullptr, n_queries, stride,
-                                        lens ? d_lens : nullptr, *p, d_rows, d_nrows, max_rows, c->blat_order, false),
+                                        lens ? d_lens.get() : nullptr, *p, d_rows, d_nrows, max_rows, c->blat_order, false),
                             s)) != hipSuccess ||
         (e = hipMemcpyAsync(rows, d_rows, sizeof(af_psl) * nr, hipMemcpyDeviceToHost, s)) != hipSuccess ||
         (e = hipMemcpyAsync(n_rows, d_nrows, 4 * n_queries, hipMemcpyDeviceToHost, s)) != hipSuccess ||
         (e = hipStreamSynchronize(s)) != hipSuccess)
-        return done(fail(c, AF_E_HIP, "af_blat: %s", hipGetErrorString(e)));
-    return done(AF_OK);
+        return fail(c, AF_E_HIP, "af_blat: %s", hipGetErrorString(e));
+    return AF_OK;
 }
 
 int af_blat_long(af_ctx *c, const af_index *ix, const uint8_t *query, int32_t len, const af_blat_params *p,
@@ -1237,10 +1105,7 @@ int af_blat_long(af_ctx *c, const af_index *ix, const uint8_t *query, int32_t le
     if (len < 0 || len > AF_BLAT_LONG_MAX) return fail(c, AF_E_INVALID, "query length %d outside [0, %d]", len, AF_BLAT_LONG_MAX);
     if (max_rows < 0 || block_cap < 0) return fail(c, AF_E_INVALID, "max_rows / block_cap out of range");
     (void)hipSetDevice(c->device);
-    if (!c->blat_caps) {
-        HIPCHK(c, hipMalloc(&c->blat_caps, sizeof(int32_t) * AF_BLAT_CAP_N));
-        HIPCHK(c, hipMemset(c->blat_caps, 0, sizeof(int32_t) * AF_BLAT_CAP_N));
-    }
+    if ((rc = ensure_blat_caps(c))) return rc;
     // the codes of both strands (strand 1: the reverse complement)
     std::vector<uint8_t> q2(2 * (size_t)len + 16, 4);
     for (int i = 0; i < len; ++i) {
@@ -1250,8 +1115,8 @@ int af_blat_long(af_ctx *c, const af_index *ix, const uint8_t *query, int32_t le
         q2[i] = x;
         q2[len + (len - 1 - i)] = x > 3 ? 4 : 3 - x;
     }
-    uint8_t *d_q2 = nullptr;
-    HIPCHK(c, hipMalloc(&d_q2, q2.size()));
+    DevBuf<uint8_t> d_q2;
+    ALLOCCHK(c, AF_E_HIP, d_q2.alloc((int64_t)q2.size()));
     std::vector<af_psl> r;
     std::vector<int32_t> seq;
     std::vector<int64_t> boff;
@@ -1260,7 +1125,7 @@ int af_blat_long(af_ctx *c, const af_index *ix, const uint8_t *query, int32_t le
     int overflow = 0;
     if (e == hipSuccess)
         e = af_blat_long_run(ix->tile, d_q2, len, *p, c->blat_caps, r, seq, boff, blk, c->n_cu, c->stream, &overflow);
-    (void)hipFree(d_q2);
+    d_q2.reset();
     if (e == hipErrorOutOfMemory) return fail(c, AF_E_NOMEM, "af_blat_long: device memory");
     if (e != hipSuccess) return fail(c, AF_E_HIP, "af_blat_long: %s", hipGetErrorString(e));
     if (overflow) return fail(c, AF_E_CAPACITY, "af_blat_long: the device row list / block arena overflowed");
@@ -1378,11 +1243,11 @@ int af_blat_query_caps(af_ctx *c, int32_t *d_counts, int64_t cap) {
 int af_blat_heavy_stats(af_ctx *c, int32_t *out) {
     if (!c || !out) return fail(c, AF_E_INVALID, "null argument");
     for (int k = 0; k < 4; ++k) out[k] = 0;
-    if (!c->blat_hv.ctrl) return AF_OK;
+    if (!c->blat_hv_ctrl) return AF_OK;
     (void)hipSetDevice(c->device);
     HIPCHK(c, hipDeviceSynchronize());
     const int32_t at[4] = {AF_BLAT_HV_STRANDS_N, AF_BLAT_HV_JOBS_N, AF_BLAT_HV_JOBS_DONE, AF_BLAT_HV_STRANDS_DONE};
-    for (int k = 0; k < 4; ++k) HIPCHK(c, hipMemcpy(out + k, c->blat_hv.ctrl + at[k], 4, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 4; ++k) HIPCHK(c, hipMemcpy(out + k, c->blat_hv_ctrl + at[k], 4, hipMemcpyDeviceToHost));
     return AF_OK;
 }
 
@@ -1483,11 +1348,9 @@ int af_genome_align_pe_device(af_ctx *c, const af_genome *g, const uint8_t *d_re
     hipStream_t s = (hipStream_t)stream;
     const GOpt o = genome_opt(&e);
     const GWork w = genome_work(c, 2 * n_pairs);
-    S2Work sw{};
-    sw.ghist = c->g_ghist; sw.pes = c->g_pes; sw.ppc = 0; sw.cstart = c->g_cstart; sw.n_chunks = c->g_nchunks;
-    sw.max_chunks = c->g_max_chunks;
-    HIPCHK(c, af_launch_s2_chunks(n_pairs, stride, d_lens, e.chunk_bases, c->g_cstart, c->g_scan, c->g_max_chunks,
-                                  c->g_nchunks, s));
+    const S2Work sw = genome_pe_work(c);
+    HIPCHK(c, af_launch_s2_chunks(n_pairs, stride, d_lens, e.chunk_bases, c->g_cs.cstart, c->g_scan, sw.max_chunks,
+                                  c->g_cs.nchunks, s));
     HIPCHK(c, af_launch_genome_regions(g->dev, d_reads, stride, d_lens, nullptr, 2 * n_pairs, *p, o, w, c->g1_scr,
                                        c->g1_threads, c->g2_scr, c->g2_waves, c->zscratch, s));
     HIPCHK(c, af_launch_genome_pe(g->dev, d_reads, stride, d_lens, nullptr, n_pairs, *p, o, w, sw, c->g2_scr,
@@ -1519,22 +1382,20 @@ int af_genome_align_pe_se_device(af_ctx *c, const af_genome *g, const uint8_t *d
         (n_pairs && (rc = ensure_genome_pe(c, n_pairs, stride, e4.chunk_bases, e4.max_ins))))
         return rc;
     hipStream_t s = (hipStream_t)stream, spe = stream_pe ? (hipStream_t)stream_pe : s;
-    if (spe != s && !c->g2_scr_pe) {
-        HIPCHK(c, hipMalloc(&c->g2_scr_pe, af_g2_slot_bytes() * (size_t)c->g2_waves));
-        HIPCHK(c, hipMalloc(&c->zscratch_pe, (size_t)(AF_MAX_READ + 1) * 1024 * (size_t)c->n_slots));
+    if (spe != s) {  // allocated once
+        ALLOCCHK(c, AF_E_HIP, c->g2_scr_pe.grow((int64_t)(af_g2_slot_bytes() * (size_t)c->g2_waves)));
+        ALLOCCHK(c, AF_E_HIP, c->zscratch_pe.grow((int64_t)(AF_MAX_READ + 1) * 1024 * c->n_slots));
     }
     if (!c->g_ev) HIPCHK(c, hipEventCreateWithFlags(&c->g_ev, hipEventDisableTiming));
     const GOpt o = genome_opt(&e4);
     const GWork w = genome_work(c, n);
     if (n_pairs)
-        HIPCHK(c, af_launch_s2_chunks(n_pairs, stride, d_lens, e4.chunk_bases, c->g_cstart, c->g_scan, c->g_max_chunks,
-                                      c->g_nchunks, s));
+        HIPCHK(c, af_launch_s2_chunks(n_pairs, stride, d_lens, e4.chunk_bases, c->g_cs.cstart, c->g_scan,
+                                      c->g_cs.max_chunks(), c->g_cs.nchunks, s));
     HIPCHK(c, af_launch_genome_regions(g->dev, d_reads, stride, d_lens, nullptr, n, *p, o, w, c->g1_scr, c->g1_threads,
                                        c->g2_scr, c->g2_waves, c->zscratch, s));
     if (n_pairs) {
-        S2Work sw{};
-        sw.ghist = c->g_ghist; sw.pes = c->g_pes; sw.ppc = 0; sw.cstart = c->g_cstart; sw.n_chunks = c->g_nchunks;
-        sw.max_chunks = c->g_max_chunks;
+        const S2Work sw = genome_pe_work(c);
         if (spe != s) {
             HIPCHK(c, hipEventRecord(c->g_ev, s));
             HIPCHK(c, hipStreamWaitEvent(spe, c->g_ev, 0));
@@ -1559,19 +1420,9 @@ int af_genome_align_pe_se_device(af_ctx *c, const af_genome *g, const uint8_t *d
 static int genome_stage(af_ctx *c, const uint8_t *reads, int64_t n_reads, int32_t stride, const int32_t *lens,
                         bool need_lens, const int32_t **d_lens) {
     const int64_t bytes = n_reads * (int64_t)stride;
-    if (bytes > c->g_cap_hbytes) {
-        af_free(c->g_hreads); c->g_hreads = nullptr; c->g_cap_hbytes = 0;
-        HIPCHK(c, hipMalloc(&c->g_hreads, bytes + 16));
-        c->g_cap_hbytes = bytes;
-    }
-    if (n_reads > c->g_cap_recs) {
-        af_free(c->g_recs); af_free(c->g_nrec); af_free(c->g_hlens);
-        c->g_recs = nullptr; c->g_nrec = nullptr; c->g_hlens = nullptr; c->g_cap_recs = 0;
-        HIPCHK(c, hipMalloc(&c->g_recs, sizeof(af_grec) * AF_G_MAX_REC * n_reads));
-        HIPCHK(c, hipMalloc(&c->g_nrec, sizeof(int32_t) * n_reads));
-        HIPCHK(c, hipMalloc(&c->g_hlens, sizeof(int32_t) * n_reads));
-        c->g_cap_recs = n_reads;
-    }
+    ALLOCCHK(c, AF_E_HIP, c->g_hreads.grow(bytes + 16));
+    if (n_reads > c->g_nrec.size())
+        ALLOCCHK(c, AF_E_HIP, dev_alloc_all({{c->g_recs, AF_G_MAX_REC * n_reads}, {c->g_hlens, n_reads}, {c->g_nrec, n_reads}}));
     HIPCHK(c, hipMemcpyAsync(c->g_hreads, reads, bytes, hipMemcpyHostToDevice, c->stream));
     *d_lens = nullptr;
     if (lens || need_lens) {
@@ -1581,7 +1432,7 @@ static int genome_stage(af_ctx *c, const uint8_t *reads, int64_t n_reads, int32_
             HIPCHK(c, hipMemcpyAsync(c->g_hlens, u.data(), sizeof(int32_t) * n_reads, hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
-        *d_lens = c->g_hlens;
+        *d_lens = c->g_hlens.get();
     }
     return AF_OK;
 }
@@ -1644,8 +1495,8 @@ int af_genome_regions(af_ctx *c, const af_genome *g, const uint8_t *reads, int64
     HIPCHK(c, hipMemcpyAsync(off.data(), c->g_reg_off, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&fill, c->g_reg_fill, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<GReg> pool((size_t)std::max<int64_t>(std::min<int64_t>(fill, c->g_reg_cap), 1));
-    if (fill > 0) HIPCHK(c, hipMemcpy(pool.data(), c->g_reg, sizeof(GReg) * std::min<int64_t>(fill, c->g_reg_cap),
+    std::vector<GReg> pool((size_t)std::max<int64_t>(std::min<int64_t>(fill, c->g_reg.size()), 1));
+    if (fill > 0) HIPCHK(c, hipMemcpy(pool.data(), c->g_reg, sizeof(GReg) * std::min<int64_t>(fill, c->g_reg.size()),
                                       hipMemcpyDeviceToHost));
     for (int64_t r = 0; r < n; ++r) {
         for (int k = 0; k < n_reg[r] && k < max_reg; ++k) {
@@ -1678,7 +1529,7 @@ int af_genome_intervals(af_ctx *c, const af_genome *g, const uint8_t *reads, int
     HIPCHK(c, hipMemcpyAsync(off.data(), c->g_iv_off, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&fill, c->g_iv_fill, sizeof fill, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int64_t nf = std::min<int64_t>((int64_t)fill, c->g_iv_cap);
+    const int64_t nf = std::min<int64_t>((int64_t)fill, c->g_iv.size());
     std::vector<GIv> pool((size_t)std::max<int64_t>(nf, 1));
     if (nf > 0) HIPCHK(c, hipMemcpy(pool.data(), c->g_iv, sizeof(GIv) * nf, hipMemcpyDeviceToHost));
     for (int64_t r = 0; r < n; ++r)
@@ -1701,17 +1552,13 @@ int af_genome_stats(af_ctx *c, int32_t *out) {
 
 // the S5 check's per-query flags, selection and select scratch for n queries
 static int ensure_s5(af_ctx *c, int64_t n_queries) {
-    if (n_queries > c->s5_cap) {
-        af_free(c->s5_keep); af_free(c->s5_sel); af_free(c->s5_temp);
-        c->s5_keep = nullptr; c->s5_sel = nullptr; c->s5_temp = nullptr; c->s5_cap = 0;
+    if (n_queries > c->s5_keep.size()) {
         const int64_t n = std::max<int64_t>(n_queries, 1 << 16);
         c->s5_temp_bytes = af_s5_temp_bytes(n);
-        HIPCHK(c, hipMalloc(&c->s5_keep, n));
-        HIPCHK(c, hipMalloc(&c->s5_sel, sizeof(int32_t) * n));
-        HIPCHK(c, hipMalloc(&c->s5_temp, std::max<size_t>(c->s5_temp_bytes, 16)));
-        c->s5_cap = n;
+        ALLOCCHK(c, AF_E_HIP, dev_alloc_all({{c->s5_sel, n}, {c->s5_temp, (int64_t)std::max<size_t>(c->s5_temp_bytes, 16)},
+                                             {c->s5_keep, n}}));
     }
-    if (!c->s5_nsel) HIPCHK(c, hipMalloc(&c->s5_nsel, sizeof(int64_t)));
+    ALLOCCHK(c, AF_E_HIP, c->s5_nsel.grow(1));
     return AF_OK;
 }
 
@@ -1793,24 +1640,12 @@ int af_s6_compact_device(af_ctx *c, const af_s6_set *pre, const uint8_t *d_live,
     if (pre->spill_cap > 0 && out->spill_cap <= 0)
         return fail(c, AF_E_INVALID, "af_s6_compact_device: pre has a spill pool, out none");
     (void)hipSetDevice(c->device);
-    if (!c->blat_caps) {
-        HIPCHK(c, hipMalloc(&c->blat_caps, sizeof(int32_t) * AF_BLAT_CAP_N));
-        HIPCHK(c, hipMemset(c->blat_caps, 0, sizeof(int32_t) * AF_BLAT_CAP_N));
-    }
-    if (pre->cap > c->s6_cap || pre->spill_cap > c->s6_spill_cap) {
-        af_free(c->s6_flag); af_free(c->s6_idx); af_free(c->s6_sflag); af_free(c->s6_sidx); af_free(c->s6_temp);
-        c->s6_flag = c->s6_idx = c->s6_sflag = c->s6_sidx = nullptr;
-        c->s6_temp = nullptr;
-        c->s6_cap = c->s6_spill_cap = 0;
+    if (int rc = ensure_blat_caps(c)) return rc;
+    if (pre->cap > c->s6_flag.size() || pre->spill_cap > c->s6_sflag.size()) {
         const int64_t n = std::max<int64_t>(pre->cap, 1 << 16), ns = std::max<int64_t>(pre->spill_cap, 1 << 16);
         c->s6_temp_bytes = std::max(af_s6_compact_temp_bytes(n), af_s6_compact_temp_bytes(ns));
-        HIPCHK(c, hipMalloc(&c->s6_flag, sizeof(int32_t) * n));
-        HIPCHK(c, hipMalloc(&c->s6_idx, sizeof(int32_t) * n));
-        HIPCHK(c, hipMalloc(&c->s6_sflag, sizeof(int32_t) * ns));
-        HIPCHK(c, hipMalloc(&c->s6_sidx, sizeof(int32_t) * ns));
-        HIPCHK(c, hipMalloc(&c->s6_temp, std::max<size_t>(c->s6_temp_bytes, 16)));
-        c->s6_cap = n;
-        c->s6_spill_cap = ns;
+        ALLOCCHK(c, AF_E_HIP, dev_alloc_all({{c->s6_flag, n}, {c->s6_idx, n}, {c->s6_sflag, ns}, {c->s6_sidx, ns},
+                                             {c->s6_temp, (int64_t)std::max<size_t>(c->s6_temp_bytes, 16)}}));
     }
     HIPCHK(c, af_launch_s6_compact(*pre, d_live, *out, max_rows, c->blat_caps, c->s6_flag, c->s6_idx, c->s6_sflag,
                                    c->s6_sidx, c->s6_temp, c->s6_temp_bytes, (hipStream_t)stream));

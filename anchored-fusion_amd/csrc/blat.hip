@@ -1216,81 +1216,59 @@ extern "C" int af_debug_blat_prof_read(int32_t *host, int64_t n) {
 }
 #endif
 
-// builds X's device arrays from d_seq (device bytes): allocations go to allocs[*na] (freed with
-// the index); returns a HIP error or hipSuccess
-hipError_t af_build_tile_index(const uint8_t *d_seq, int64_t n, int32_t step, DevTile *X, void **allocs, int *na,
+// builds X's device arrays from d_seq (device bytes): they are added to `owned` (freed with the
+// index); returns a HIP error or hipSuccess
+hipError_t af_build_tile_index(const uint8_t *d_seq, int64_t n, int32_t step, DevTile *X, DevBufList &owned,
                                hipStream_t s) {
     hipError_t e;
-    const int64_t n_tiles = n >= TILE ? (n - TILE) / step + 1 : 0;
+    const int64_t n_tiles = n >= TILE ? (n - TILE) / step + 1 : 0, nt = n_tiles > 0 ? n_tiles : 1;
     const int64_t nb = (n >> 6) + 2;  // N counts before each 64-base block (and one past the last)
     uint8_t *T = nullptr;
     uint32_t *start = nullptr, *pos = nullptr, *ncum = nullptr, *nnext = nullptr;
     uint64_t *nmask = nullptr;
-    uint32_t *keys = nullptr, *keys2 = nullptr, *pos2 = nullptr, *cnt = nullptr, *rf = nullptr, *rm = nullptr;
-    void *temp = nullptr;
-    auto cleanup = [&]() {
-        if (rf) (void)hipFree(rf);
-        if (rm) (void)hipFree(rm);
-        if (keys) (void)hipFree(keys);
-        if (keys2) (void)hipFree(keys2);
-        if (pos2) (void)hipFree(pos2);
-        if (cnt) (void)hipFree(cnt);
-        if (temp) (void)hipFree(temp);
-    };
-    if ((e = hipMalloc(&T, (size_t)n)) != hipSuccess) return e;
-    allocs[(*na)++] = T;
-    if ((e = hipMalloc(&start, sizeof(uint32_t) * (NKEYS + 1))) != hipSuccess) return e;
-    allocs[(*na)++] = start;
-    if ((e = hipMalloc(&pos, sizeof(uint32_t) * (size_t)(n_tiles > 0 ? n_tiles : 1))) != hipSuccess) return e;
-    allocs[(*na)++] = pos;
-    if ((e = hipMalloc(&ncum, sizeof(uint32_t) * (size_t)nb)) != hipSuccess) return e;
-    allocs[(*na)++] = ncum;
-    if ((e = hipMalloc(&nmask, sizeof(uint64_t) * (size_t)nb)) != hipSuccess) return e;
-    allocs[(*na)++] = nmask;
-    if ((e = hipMalloc(&nnext, sizeof(uint32_t) * (size_t)nb)) != hipSuccess) return e;
-    allocs[(*na)++] = nnext;
-    if ((e = hipMalloc(&keys, sizeof(uint32_t) * (size_t)(n_tiles > 0 ? n_tiles : 1))) != hipSuccess ||
-        (e = hipMalloc(&keys2, sizeof(uint32_t) * (size_t)(n_tiles > 0 ? n_tiles : 1))) != hipSuccess ||
-        (e = hipMalloc(&pos2, sizeof(uint32_t) * (size_t)(n_tiles > 0 ? n_tiles : 1))) != hipSuccess ||
-        (e = hipMalloc(&cnt, sizeof(uint32_t) * (NKEYS + 1))) != hipSuccess ||
-        (e = hipMalloc(&rf, sizeof(uint32_t) * (size_t)nb)) != hipSuccess ||
-        (e = hipMalloc(&rm, sizeof(uint32_t) * (size_t)nb)) != hipSuccess) {
-        cleanup();
+    DevBuf<uint32_t> keys, keys2, pos2, cnt, rf, rm;
+    DevBuf<uint8_t> temp;
+    if ((e = dev_list_alloc(owned, (size_t)n, &T)) != hipSuccess ||
+        (e = dev_list_alloc(owned, sizeof(uint32_t) * (NKEYS + 1), &start)) != hipSuccess ||
+        (e = dev_list_alloc(owned, sizeof(uint32_t) * (size_t)nt, &pos)) != hipSuccess ||
+        (e = dev_list_alloc(owned, sizeof(uint32_t) * (size_t)nb, &ncum)) != hipSuccess ||
+        (e = dev_list_alloc(owned, sizeof(uint64_t) * (size_t)nb, &nmask)) != hipSuccess ||
+        (e = dev_list_alloc(owned, sizeof(uint32_t) * (size_t)nb, &nnext)) != hipSuccess ||
+        (e = dev_alloc_all({{keys, nt}, {keys2, nt}, {pos2, nt}, {cnt, NKEYS + 1}, {rf, nb}, {rm, nb}})) != hipSuccess)
         return e;
-    }
     size_t tb_sort = 0, tb_scan = 0, tb_scan2 = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, keys, keys2, pos, pos2, n_tiles, 0, 2 * TILE + 1);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, cnt, start, NKEYS + 1);
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, keys.get(), keys2.get(), pos, pos2.get(), n_tiles, 0, 2 * TILE + 1);
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, cnt.get(), start, NKEYS + 1);
     (void)hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan2, ncum, ncum, nb);
     size_t tb_min = 0;
-    (void)hipcub::DeviceScan::InclusiveScan(nullptr, tb_min, rf, rm, MinU32(), nb - 1);
+    (void)hipcub::DeviceScan::InclusiveScan(nullptr, tb_min, rf.get(), rm.get(), MinU32(), nb - 1);
     size_t tb = std::max(std::max(tb_sort, tb_min), std::max(tb_scan, tb_scan2));
-    if ((e = hipMalloc(&temp, tb > 0 ? tb : 16)) != hipSuccess) { cleanup(); return e; }
+    if ((e = temp.alloc(tb > 0 ? (int64_t)tb : 16)) != hipSuccess) return e;
     const int bs = 256;
     if ((e = hipMemsetAsync(cnt, 0, sizeof(uint32_t) * (NKEYS + 1), s)) != hipSuccess ||
         (e = hipMemsetAsync(ncum, 0, sizeof(uint32_t) * (size_t)nb, s)) != hipSuccess ||
-        (e = hipMemsetAsync(nnext, 0xFF, sizeof(uint32_t) * (size_t)nb, s)) != hipSuccess) { cleanup(); return e; }
+        (e = hipMemsetAsync(nnext, 0xFF, sizeof(uint32_t) * (size_t)nb, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_tile_codes, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, s, d_seq, n, T);
     if (n_tiles > 0)
         hipLaunchKernelGGL(k_tile_keys, dim3((unsigned)((n_tiles + bs - 1) / bs)), dim3(bs), 0, s, T, n, step, n_tiles,
-                           keys, pos2, cnt);
+                           keys.get(), pos2.get(), cnt.get());
     hipLaunchKernelGGL(k_tile_nblocks, dim3((unsigned)((nb - 1 + bs - 1) / bs)), dim3(bs), 0, s, T, n, nb - 1, nmask,
-                       ncum, rf);
-    if ((e = hipGetLastError()) != hipSuccess) { cleanup(); return e; }
+                       ncum, rf.get());
+    if ((e = hipGetLastError()) != hipSuccess) return e;
     size_t t1 = tb;
     if (n_tiles > 0 &&
-        (e = hipcub::DeviceRadixSort::SortPairs(temp, t1, keys, keys2, pos2, pos, n_tiles, 0, 2 * TILE + 1, s)) !=
-            hipSuccess) { cleanup(); return e; }
+        (e = hipcub::DeviceRadixSort::SortPairs(temp.get(), t1, keys.get(), keys2.get(), pos2.get(), pos, n_tiles, 0,
+                                                2 * TILE + 1, s)) != hipSuccess)
+        return e;
     t1 = tb;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(temp, t1, cnt, start, NKEYS + 1, s)) != hipSuccess) { cleanup(); return e; }
+    if ((e = hipcub::DeviceScan::ExclusiveSum(temp.get(), t1, cnt.get(), start, NKEYS + 1, s)) != hipSuccess) return e;
     t1 = tb;
-    if ((e = hipcub::DeviceScan::InclusiveSum(temp, t1, ncum, ncum, nb, s)) != hipSuccess) { cleanup(); return e; }
+    if ((e = hipcub::DeviceScan::InclusiveSum(temp.get(), t1, ncum, ncum, nb, s)) != hipSuccess) return e;
     t1 = tb;
-    if ((e = hipcub::DeviceScan::InclusiveScan(temp, t1, rf, rm, MinU32(), nb - 1, s)) != hipSuccess) { cleanup(); return e; }
-    hipLaunchKernelGGL(k_tile_nnext, dim3((unsigned)((nb - 1 + bs - 1) / bs)), dim3(bs), 0, s, rm, nb - 1, nnext);
-    if ((e = hipGetLastError()) != hipSuccess) { cleanup(); return e; }
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) { cleanup(); return e; }
-    cleanup();
+    if ((e = hipcub::DeviceScan::InclusiveScan(temp.get(), t1, rf.get(), rm.get(), MinU32(), nb - 1, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_tile_nnext, dim3((unsigned)((nb - 1 + bs - 1) / bs)), dim3(bs), 0, s, rm.get(), nb - 1, nnext);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
     X->T = T; X->start = start; X->pos = pos; X->ncum = ncum; X->nmask = nmask; X->nnext = nnext; X->n = n;
     X->step = step;
     return hipSuccess;
