@@ -45,6 +45,9 @@ EXPORTS = (
     "af_genome_align_se_ids_device", "af_genome_align_pe_se_device", "af_genome_intervals", "af_s5_rules_host", "af_blat_caps", "af_blat_spill",
     "af_blat_query_caps", "af_s6_queries_device", "af_s6_check_device", "af_s6_compact_device",
     "af_blat_device_begin", "af_blat_device_end", "af_blat_long", "af_blat_heavy_stats",
+    "af_fastq_dev_open", "af_fastq_dev_next", "af_fastq_dev_export", "af_fastq_dev_error", "af_fastq_dev_close",
+    "af_fastq_dev_times",
+    "af_bgzf_inflate_device", "af_inflate_host",
 )
 AF_G_MAX_REC = 8
 AF_GSTAT_N = 4
@@ -235,6 +238,22 @@ def lib():
     L.af_blat_long.restype = ctypes.c_int
     L.af_blat_heavy_stats.argtypes = [_vp, _vp]
     L.af_blat_heavy_stats.restype = ctypes.c_int
+    L.af_fastq_dev_open.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, _i64, ctypes.POINTER(_vp)]
+    L.af_fastq_dev_open.restype = ctypes.c_int
+    L.af_fastq_dev_next.argtypes = [_vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i32), ctypes.POINTER(_i64)]
+    L.af_fastq_dev_next.restype = ctypes.c_int
+    L.af_fastq_dev_export.argtypes = [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp]
+    L.af_fastq_dev_export.restype = ctypes.c_int
+    L.af_fastq_dev_error.argtypes = [_vp]
+    L.af_fastq_dev_error.restype = ctypes.c_char_p
+    L.af_fastq_dev_close.argtypes = [_vp]
+    L.af_fastq_dev_close.restype = None
+    L.af_fastq_dev_times.argtypes = [_vp, _vp]
+    L.af_fastq_dev_times.restype = ctypes.c_int
+    L.af_bgzf_inflate_device.argtypes = [_vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i32)]
+    L.af_bgzf_inflate_device.restype = ctypes.c_int
+    L.af_inflate_host.argtypes = [_vp, _i64, _vp, _i64, ctypes.POINTER(_i64), _vp]
+    L.af_inflate_host.restype = ctypes.c_int
     _L = L
     return L
 

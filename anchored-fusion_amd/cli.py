@@ -47,6 +47,8 @@ def parser():
     ap.add_argument("--thread", type=str, default="1", help="bwa threads: sets the 10,000,000 x T base input chunk")
     ap.add_argument("--gpu_number", type=str, default="-1", help="GPU index (-1: the first visible GPU)")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node to shard the pairs over (one process each)")
+    ap.add_argument("--gpu_ingest", action="store_true",
+                    help="inflate and parse BGZF / plain 4-line FASTQ on the GPU (single GPU; other input: host reader)")
     return ap
 
 
@@ -154,7 +156,7 @@ def main(argv=None):
     try:
         pipeline.run(args.file_anchored_cds, args.fastq1, args.fastq2, args.file_ref_seq, args.file_ref_ann,
                      args.out_folder, gene_names=args.gene_names or None, device=dev, filt=_filter(args, dev),
-                     chunk_bases=_chunk_bases(args))
+                     chunk_bases=_chunk_bases(args), gpu_ingest=args.gpu_ingest)
     finally:
         _finish()
     return 0

@@ -7,6 +7,10 @@
 #include "../../include/afgpu.h"
 #include "dev_buf.h"
 
+// af_ctx is private to api.hip; the other files' entry points reach these two through it
+int af_ctx_device_id(const af_ctx *c);
+void af_ctx_set_error(af_ctx *c, const char *msg);
+
 #define AF_NEG_INF (-0x40000000)
 #define AF_SEED_BTILE 2048      // reads per workgroup tile in the seed filter
 #define AF_SEED_WAVES 16        // waves per seed-filter workgroup (1024 threads)

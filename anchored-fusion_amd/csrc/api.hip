@@ -152,6 +152,10 @@ struct af_index {
     DevBufList owned;      // every device array dev / s2 / tile point to
 };
 
+// for the entry points outside this file (ingest_dev.hip): the context's device and message
+int af_ctx_device_id(const af_ctx *c) { return c->device; }
+void af_ctx_set_error(af_ctx *c, const char *msg) { c->err = msg; }
+
 namespace {
 
 int fail(af_ctx *c, int code, const char *fmt, ...) {

@@ -166,7 +166,8 @@ def iter_pairs(fq1, fq2, batch_pairs=1 << 20, threads=0):
 
 
 class NotBGZF(ValueError):
-    """A sharded read of input that is not BGZF (blocked gzip)."""
+    """Input that a BGZF-only reader declines (the sharded reader: not blocked gzip; the device
+    reader: that, or records that are not 4-line FASTQ): read it with ``read_pairs``."""
 
 
 def read_part(path, part, parts, threads=0):
@@ -222,6 +223,77 @@ def read_pairs(fq1, fq2, threads=0):
     lens = np.concatenate([x for _, _, x in parts]) if len(parts) > 1 else parts[0][2]
     names = Names.concat([nm for nm, _, _ in parts])
     return names, reads, (None if (lens == stride).all() else lens)
+
+
+def read_pairs_device(fq1, fq2, device=0, batch_bytes=0, batch_pairs=1 << 20, times=None):
+    """``read_pairs`` on the GPU (csrc/ingest_dev.hip, af_fastq_dev_*): a BGZF or plain
+    uncompressed pair of 4-line FASTQ files is inflated, parsed and packed on ``device``.
+
+    Returns ``(names, reads_t[2N, stride] uint8, lens_t[2N] int32 or None)`` with the two arrays as
+    torch tensors on the device, equal to ``read_pairs``' byte for byte.  Raises ``NotBGZF`` for
+    input the device reader declines (gzip that is not BGZF, records that are not 4 lines): read it
+    with ``read_pairs``; ``ValueError`` with the reader's message for malformed input.
+    batch_bytes: compressed bytes inflated per round (0: the library's default).  times: a dict
+    that receives the reader's seconds per phase (read, h2d, inflate, parse, export)."""
+    import ctypes
+
+    import torch
+
+    from . import _lib
+    L = _lib.lib()
+    dev = torch.device("cuda", int(device))
+    ctx, h = ctypes.c_void_p(), ctypes.c_void_p()
+    _lib.check(None, L.af_ctx_create(int(device), ctypes.byref(ctx)), "af_ctx_create")
+    parts = []
+    try:
+        rc = L.af_fastq_dev_open(ctx, os.fsencode(fq1), os.fsencode(fq2), int(batch_bytes), ctypes.byref(h))
+        msg = lambda: L.af_fastq_dev_error(h).decode(errors="replace")  # noqa: E731
+        if rc == _lib.AF_E_UNSUPPORTED:
+            raise NotBGZF(msg())
+        if rc != 0:
+            raise _lib.AFError(f"af_fastq_dev_open failed (rc={rc}): {msg()}")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        while True:
+            n, ml, nb = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int64()
+            rc = L.af_fastq_dev_next(h, int(batch_pairs), ctypes.byref(n), ctypes.byref(ml), ctypes.byref(nb))
+            if rc == _lib.AF_E_UNSUPPORTED:
+                raise NotBGZF(msg())
+            if rc != 0:
+                raise ValueError(f"{fq1}, {fq2}: {msg()}")
+            if n.value == 0:
+                break
+            stride = max(int(ml.value), 1)
+            reads = torch.empty((2 * n.value, stride), dtype=torch.uint8, device=dev)
+            lens = torch.empty(2 * n.value, dtype=torch.int32, device=dev)
+            arena = np.empty(max(int(nb.value), 1), dtype=np.uint8)
+            off = np.empty(n.value, dtype=np.int64)
+            rc = L.af_fastq_dev_export(h, stride, reads.data_ptr(), lens.data_ptr(), arena.ctypes.data, arena.size,
+                                       off.ctypes.data, stream)
+            if rc != 0:
+                raise _lib.AFError(f"af_fastq_dev_export failed (rc={rc}): {msg()}")
+            parts.append((Names(arena.tobytes(), off), reads, lens))
+    finally:
+        if h:
+            if times is not None:
+                sec = (ctypes.c_double * 5)()
+                L.af_fastq_dev_times(h, sec)
+                times.update(zip(("read", "h2d", "inflate", "parse", "export"), (float(v) for v in sec)))
+            L.af_fastq_dev_close(h)
+        L.af_ctx_destroy(ctx)
+    if not parts:
+        return Names(b"", np.zeros(0, np.int64)), torch.full((0, 1), ord("N"), dtype=torch.uint8, device=dev), None
+    stride = max(r.shape[1] for _, r, _ in parts)
+    if all(r.shape[1] == stride for _, r, _ in parts):
+        reads = torch.cat([r for _, r, _ in parts]) if len(parts) > 1 else parts[0][1]
+    else:
+        reads = torch.full((sum(r.shape[0] for _, r, _ in parts), stride), ord("N"), dtype=torch.uint8, device=dev)
+        row = 0
+        for _, r, _ in parts:
+            reads[row:row + r.shape[0], :r.shape[1]] = r
+            row += r.shape[0]
+    lens = torch.cat([x for _, _, x in parts]) if len(parts) > 1 else parts[0][2]
+    names = Names.concat([nm for nm, _, _ in parts])
+    return names, reads, (None if bool((lens == stride).all()) else lens)
 
 
 def anchor_sequence(path, index=0):

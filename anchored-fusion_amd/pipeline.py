@@ -37,7 +37,7 @@ import re
 from . import blocks as blk
 from . import genome_check, partner, report, splitreads
 from .annotation import ExonIndex
-from .io import read_fasta, read_pairs
+from .io import NotBGZF, read_fasta, read_pairs, read_pairs_device
 
 _COMP = str.maketrans("ACGTNacgtn", "TGCANtgcan")
 
@@ -366,6 +366,23 @@ def upload_reads(reads, lens, device):
     return reads_t, lens_t, pair_bases
 
 
+def device_reads(reads_t, lens_t):
+    """upload_reads' result from what io.read_pairs_device left in HBM: the rows padded to a multiple
+    of 8 bytes, the lengths, and the pairs' base counts."""
+    import torch
+    n, width = reads_t.shape
+    stride = max(8, -(-width // 8) * 8)
+    if stride != width:
+        padded = torch.full((n, stride), ord("N"), dtype=torch.uint8, device=reads_t.device)
+        padded[:, :width] = reads_t
+        reads_t = padded
+    if lens_t is None:
+        lens_t = torch.full((n,), width, dtype=torch.int32, device=reads_t.device)
+    pair_bases = lens_t.to(torch.int64).reshape(-1, 2).sum(dim=1).cpu().numpy()
+    torch.cuda.synchronize(reads_t.device)
+    return reads_t, lens_t, pair_bases
+
+
 def dist_world(group=None):
     """(rank, world) of the torch.distributed job this process is in, (0, 1) outside one."""
     try:
@@ -378,7 +395,8 @@ def dist_world(group=None):
 
 
 def run(anchored_cds, fastq1, fastq2, ref_seq, ref_ann, out_folder, gene_names=None, device=0, searches=None,
-        aligner_factory=None, log=print, group=None, filt=None, chunk_bases=10_000_000, backend_factory=None):
+        aligner_factory=None, log=print, group=None, filt=None, chunk_bases=10_000_000, backend_factory=None,
+        gpu_ingest=False):
     """All genes of --file_anchored_cds; writes <out>/<G>_fusion/<G>_fusion_predictions*.txt.
 
     Inside a torch.distributed job of N > 1 ranks (cli --gpus N: one process per GPU, `device`
@@ -388,7 +406,10 @@ def run(anchored_cds, fastq1, fastq2, ref_seq, ref_ann, out_folder, gene_names=N
 
     chunk_bases: bwa's input chunk, 10,000,000 x --thread (AF:182/188 `bwa mem -t T`): S2 and S4
     estimate insert sizes per chunk, so the records depend on it as the reference's do.
-    backend_factory (sharded runs): the per-rank dist_discover backend, default gpu_backend."""
+    backend_factory (sharded runs): the per-rank dist_discover backend, default gpu_backend.
+    gpu_ingest (single-GPU device path only): the FASTQ pair is inflated, parsed and packed on the GPU
+    (io.read_pairs_device) when it is BGZF or plain 4-line FASTQ; other input falls back to the host
+    reader."""
     rank, world = dist_world(group)
     if world > 1:
         return _run_sharded(anchored_cds, fastq1, fastq2, ref_seq, ref_ann, out_folder, gene_names, device,
@@ -404,15 +425,28 @@ def run(anchored_cds, fastq1, fastq2, ref_seq, ref_ann, out_folder, gene_names=N
     log(f"genome and annotation read: {len(genome)} contigs, {sum(len(s) for _, s in genome)} bp, "
         f"{len(gtf)} GTF lines ({time.perf_counter() - t0:.1f} s)")
     t0 = time.perf_counter()
-    names, reads, lens = read_pairs(fastq1, fastq2)
-    log(f"ingest: {reads.shape[0] // 2} pairs ({time.perf_counter() - t0:.1f} s)")
     # the device path (S2-S6 in HBM) unless a test injects host backends
     on_device = aligner_factory is None and (searches is None or getattr(searches, "on_device", False))
+    dev_reads = reads = lens = None
+    if gpu_ingest and on_device:
+        try:
+            names, reads_t, lens_t = read_pairs_device(fastq1, fastq2, device)
+            log(f"ingest: {reads_t.shape[0] // 2} pairs ({time.perf_counter() - t0:.1f} s, device reader)")
+            dev_reads = device_reads(reads_t, lens_t) if reads_t.shape[0] else None
+            if dev_reads is None:
+                import numpy as np
+                reads = np.full((0, 1), ord("N"), np.uint8)
+        except NotBGZF as ex:
+            log(f"ingest: the device reader declined the input ({ex}); host reader")
+    if dev_reads is None and reads is None:
+        names, reads, lens = read_pairs(fastq1, fastq2)
+        log(f"ingest: {reads.shape[0] // 2} pairs ({time.perf_counter() - t0:.1f} s)")
     if searches is None:
         searches = Searches(genome, device=device, chunk_bases=chunk_bases)
     if aligner_factory is None:
         aligner_factory = _default_aligner(device, chunk_bases)
-    dev_reads = upload_reads(reads, lens, device) if on_device and reads.shape[0] else None
+    if dev_reads is None:
+        dev_reads = upload_reads(reads, lens, device) if on_device and reads.shape[0] else None
     if dev_reads is not None:
         reads = lens = None  # the device copy is the one the genes read (15 GB at configs[2])
     results = {}

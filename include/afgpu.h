@@ -510,6 +510,43 @@ int af_fastq_part_export(af_fastq_part *p, int32_t stride, uint8_t *seqs, int32_
 const char *af_fastq_part_error(const af_fastq_part *p);
 void af_fastq_part_free(af_fastq_part *p);
 
+/* Paired FASTQ ingest on the GPU (ingest_dev.hip): the af_fastq_* reader with the inflate, the
+ * CRC32 check, the record parser, the name rules and the row packing on the device, so that only
+ * compressed bytes cross to it and the rows land in device memory.  Input: a BGZF pair or a plain
+ * uncompressed pair, holding strict 4-line FASTQ records.  AF_E_UNSUPPORTED (from open: gzip that
+ * is not BGZF; from next: multi-line records, FASTA records, blank lines, a quality line of another
+ * length) means "read these files with af_fastq_*": the device reader never guesses.  Other errors
+ * (a corrupt BGZF block, files of different length, mates with different names -- the host
+ * reader's messages) are AF_E_INVALID with the text in af_fastq_dev_error, also after a failed
+ * open, whose handle must still be closed.
+ * batch_bytes: compressed bytes inflated per round (0: 32 MiB).  af_fastq_dev_next makes the next
+ * <= max_pairs pairs ready (*n_pairs = 0 at the end) and reports the longest read and the name
+ * bytes; af_fastq_dev_export writes them: rows 2k / 2k + 1 of `stride` bytes ('N'-padded) to
+ * d_reads and lens to d_lens (device memory, enqueued on `stream`), names and name_off (host
+ * memory); any output may be NULL.  It returns after `stream` has finished them. */
+typedef struct af_fastq_dev af_fastq_dev;
+int af_fastq_dev_open(af_ctx *ctx, const char *fq1, const char *fq2, int64_t batch_bytes, af_fastq_dev **out);
+int af_fastq_dev_next(af_fastq_dev *f, int64_t max_pairs, int64_t *n_pairs, int32_t *max_len, int64_t *names_bytes);
+int af_fastq_dev_export(af_fastq_dev *f, int32_t stride, uint8_t *d_reads, int32_t *d_lens, char *names,
+                        int64_t names_cap, int64_t *name_off, void *stream);
+const char *af_fastq_dev_error(const af_fastq_dev *f);
+void af_fastq_dev_close(af_fastq_dev *f);
+/* seconds the handle has spent so far in: [0] reading the files, [1] host-to-device copies,
+ * [2] inflate + CRC32, [3] line / record parsing and the name check, [4] export (pack, names) */
+#define AF_FASTQ_DEV_TIMES 5
+int af_fastq_dev_times(const af_fastq_dev *f, double *out);
+/* Every member of a BGZF file image (host bytes) inflated and CRC-checked on the device into out
+ * (host, out_cap bytes); *n_out = the inflated size.  A corrupt member: AF_E_INVALID and
+ * *bad_member = its index (else -1); bytes that are not BGZF members: AF_E_UNSUPPORTED. */
+int af_bgzf_inflate_device(af_ctx *ctx, const uint8_t *file_bytes, int64_t n, uint8_t *out, int64_t out_cap,
+                           int64_t *n_out, int32_t *bad_member);
+/* Test hook: ONE BGZF member (header, deflate stream, trailer; n bytes) inflated on the host by the
+ * decoder the kernel runs (one source, compiled for the host too), CRC32 and ISIZE checked.  stats
+ * (8 int32; may be NULL): the stored, fixed and dynamic deflate blocks, the longest literal/length
+ * code, the largest distance, the matches with distance < length, the longest match, and the
+ * decoder's own error code (0: none).  On an error nothing is written to out.  Not a product path. */
+int af_inflate_host(const uint8_t *member, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int32_t *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,12 +6,16 @@ its background is scaled up with vectorised fragments of the same sources, writt
 alone and `pipeline.run` (ingest -> S2 on the GPU -> S3-S8 -> Final_fusion tables) on the GPU
 box's host CPU share.  Prints one JSON line.
 
-    python scripts/e2e_bench.py [pairs] [out.json]
+    python scripts/e2e_bench.py [pairs] [out.json] [--gpu-ingest]
+
+--gpu-ingest: pipeline.run reads the pair with the device reader (io.read_pairs_device) and the
+ingest-only figure times that reader.
 """
 import json
 import os
 import struct
 import sys
+import tempfile
 import time
 import zlib
 from multiprocessing import Pool
@@ -52,13 +56,11 @@ def fastq_bytes(tag, mate, seqs):
     return rec.tobytes()
 
 
-def main():
-    n_pairs = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
-    out = sys.argv[2] if len(sys.argv) > 2 else None
+def write_world(n_pairs, folder):
+    """The world's files with its background scaled to n_pairs pairs, the pair as BGZF:
+    (paths, truth, {1: fq1, 2: fq2}, read length, seconds)."""
     from fusion_world import make_world
     from anchored_fusion_amd import io as afio
-    from anchored_fusion_amd import pipeline
-    folder = os.path.join(os.environ.get("TMPDIR", "/tmp"), "af_e2e")
     t0 = time.perf_counter()
     paths, truth = make_world(folder, n_fusion=2000, n_anchor=1500, n_background=2000)
     # scale the background: fragments of the world's genome (all four contigs), 0.5 % errors
@@ -85,22 +87,35 @@ def main():
             buf = fastq_bytes("w", mate, small) + fastq_bytes("bgx", mate, big)
             fq[mate] = os.path.join(folder, f"big_{mate}.fastq.gz")
             write_bgzf(fq[mate], buf, pool)
-    t_gen = time.perf_counter() - t0
+    return paths, truth, fq, int(L), time.perf_counter() - t0
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    gpu_ingest = "--gpu-ingest" in sys.argv[1:]
+    n_pairs = int(args[0]) if args else 1_000_000
+    out = args[1] if len(args) > 1 else None
+    from anchored_fusion_amd import io as afio
+    from anchored_fusion_amd import pipeline
+    folder = os.path.join(tempfile.gettempdir(), "af_e2e")
+    paths, truth, fq, L, t_gen = write_world(n_pairs, folder)
     # ingest alone, then the whole pipeline (its own ingest included)
     t0 = time.perf_counter()
-    names, reads, lens = afio.read_pairs(fq[1], fq[2])
+    names, reads, lens = afio.read_pairs_device(fq[1], fq[2], 0) if gpu_ingest else afio.read_pairs(fq[1], fq[2])
     t_ingest = time.perf_counter() - t0
     assert reads.shape[0] == 2 * n_pairs
     del names, reads, lens
     outdir = os.path.join(folder, "out")
     t0 = time.perf_counter()
-    pipeline.run(paths["anchor"], fq[1], fq[2], paths["genome"], paths["gtf"], outdir, log=lambda *_: None)
+    pipeline.run(paths["anchor"], fq[1], fq[2], paths["genome"], paths["gtf"], outdir, log=lambda *_: None,
+                 gpu_ingest=gpu_ingest)
     t_run = time.perf_counter() - t0
     rows = [ln.split("\t") for ln in open(os.path.join(outdir, "BCRX_fusion", "BCRX_fusion_predictions_abridged.txt"))]
     hit = [r for r in rows[1:] if "ABLX" in r[0]]
     res = {
         "leg": "end to end: BGZF FASTQ pair -> io ingest -> S2 on the GPU (host-buffer API) -> S3-S8 -> "
                "Final_fusion tables (pipeline.run, one anchor)",
+        "gpu_ingest": gpu_ingest,
         "pairs": n_pairs, "read_len": int(L), "fastq_gz_bytes": os.path.getsize(fq[1]) + os.path.getsize(fq[2]),
         "wall_s": round(t_run, 3), "pairs_per_s": round(n_pairs / t_run, 1),
         "ingest_only_s": round(t_ingest, 3), "ingest_pairs_per_s": round(n_pairs / t_ingest, 1),

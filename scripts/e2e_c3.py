@@ -9,6 +9,10 @@ BGZF FASTQ (--fusion-frac of them from the anchor fusions, 0.1 % by default).  T
 lines carry each phase's time.  Prints one JSON line.
 
     python scripts/e2e_c3.py [--pairs 50000000] [--scale 1.0] [--out gpurun_out/e2e_c3.json]
+
+With --gpu-ingest the script runs pipeline.run a second time on the same files with the device reader
+(gpu_ingest=True) and prints a second JSON line (written to <out minus .json>_gpu_ingest.json), so
+both readers are timed in one session on one set of inputs.
 """
 import argparse
 import json
@@ -130,6 +134,8 @@ def main():
                          "junction, where the reference's split-read clustering, functions.py:771-951, is "
                          "quadratic in Python whatever the aligner)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--gpu-ingest", action="store_true",
+                    help="also run with the device reader on the same inputs (a second JSON line)")
     ap.add_argument("--folder", default=os.path.join(os.environ.get("TMPDIR", "/tmp"), "af_e2e_c3"))
     args = ap.parse_args()
     t_start = time.perf_counter()
@@ -141,29 +147,33 @@ def main():
         print(f"[{t:8.1f} s] {msg}", flush=True)
     from anchored_fusion_amd import pipeline
     paths, gene, junctions, t_reads = write_inputs(args.folder, args.pairs, args.scale, log, args.fusion_frac)
-    outdir = os.path.join(args.folder, "out")
-    t0 = time.perf_counter()
-    pipeline.run(paths["anchor"], paths["fq1"], paths["fq2"], paths["genome"], paths["gtf"], outdir, log=log)
-    t_run = time.perf_counter() - t0
-    tab = os.path.join(outdir, f"{gene}_fusion", f"{gene}_fusion_predictions_abridged.txt")
-    rows = [ln.rstrip("\n").split("\t") for ln in open(tab)] if os.path.exists(tab) else []
-    partners = sorted({r[0] for r in rows[1:]})
-    res = {
-        "leg": "end to end at configs[2] size: BGZF FASTQ pair + genome FASTA + GTF on disk -> pipeline.run "
-               "(native ingest, GPU genome / tile indexes, homologs, S2-S6 in HBM, host stages) -> tables",
-        "pairs": args.pairs, "read_len": 150, "genome_scale": args.scale, "fusion_frac": args.fusion_frac,
-        "fastq_gz_bytes": os.path.getsize(paths["fq1"]) + os.path.getsize(paths["fq2"]),
-        "wall_s": round(t_run, 1), "pairs_per_s": round(args.pairs / t_run, 1),
-        "phases": [m for m in marks if m[0] >= round(t0 - t_start, 1)],
-        "predictions": len(rows) - 1 if rows else 0, "partners": partners[:20],
-        "planted_fusions": len(junctions), "inputs_written_s": round(t_reads, 1),
-        "host_threads": int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or os.cpu_count(),
-    }
-    line = json.dumps(res)
-    print(line, flush=True)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
+    for gpu_ingest in ((False, True) if args.gpu_ingest else (False,)):
+        outdir = os.path.join(args.folder, "out_gpu_ingest" if gpu_ingest else "out")
+        t0 = time.perf_counter()
+        pipeline.run(paths["anchor"], paths["fq1"], paths["fq2"], paths["genome"], paths["gtf"], outdir, log=log,
+                     gpu_ingest=gpu_ingest)
+        t_run = time.perf_counter() - t0
+        tab = os.path.join(outdir, f"{gene}_fusion", f"{gene}_fusion_predictions_abridged.txt")
+        rows = [ln.rstrip("\n").split("\t") for ln in open(tab)] if os.path.exists(tab) else []
+        partners = sorted({r[0] for r in rows[1:]})
+        res = {
+            "leg": "end to end at configs[2] size: BGZF FASTQ pair + genome FASTA + GTF on disk -> pipeline.run "
+                   "(native ingest, GPU genome / tile indexes, homologs, S2-S6 in HBM, host stages) -> tables",
+            "gpu_ingest": gpu_ingest,
+            "pairs": args.pairs, "read_len": 150, "genome_scale": args.scale, "fusion_frac": args.fusion_frac,
+            "fastq_gz_bytes": os.path.getsize(paths["fq1"]) + os.path.getsize(paths["fq2"]),
+            "wall_s": round(t_run, 1), "pairs_per_s": round(args.pairs / t_run, 1),
+            "phases": [m for m in marks if m[0] >= round(t0 - t_start, 1)],
+            "predictions": len(rows) - 1 if rows else 0, "partners": partners[:20],
+            "planted_fusions": len(junctions), "inputs_written_s": round(t_reads, 1),
+            "host_threads": int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or os.cpu_count(),
+        }
+        line = json.dumps(res)
+        print(line, flush=True)
+        if args.out:
+            path = args.out if not gpu_ingest else os.path.splitext(args.out)[0] + "_gpu_ingest.json"
+            with open(path, "w") as fh:
+                fh.write(line + "\n")
 
 
 if __name__ == "__main__":
