@@ -320,6 +320,8 @@ hipError_t af_launch_genome_pe(const DevGenome &G, const uint8_t *reads, int32_t
 hipError_t af_launch_s2_pestat(const S2Work &w, int32_t max_ins, hipStream_t s);
 // test hook af_debug_kbtree (bwa_genome.hip), store 0: the kbtree over the S2 store (s2.hip)
 hipError_t af_launch_debug_kbtree_s2(const int64_t *pos, int n, int32_t *lower, int32_t *order, int32_t *count);
+// test hook af_debug_g_rid (bwa_genome.hip): af_genome is private to api.hip
+const DevGenome *af_genome_dev(const af_genome *g);
 
 // launch helpers (defined in the .hip files)
 // ctrl (AF_CTRL_BYTES, one 128-B line per word, no memsets on the hot path):

@@ -155,6 +155,7 @@ struct af_index {
 // for the entry points outside this file (ingest_dev.hip): the context's device and message
 int af_ctx_device_id(const af_ctx *c) { return c->device; }
 void af_ctx_set_error(af_ctx *c, const char *msg) { c->err = msg; }
+const DevGenome *af_genome_dev(const af_genome *g) { return g ? &g->dev : nullptr; }
 
 namespace {
 

@@ -2707,6 +2707,53 @@ extern "C" int af_debug_kbtree(const int64_t *pos, int32_t n, int32_t store, int
     return rc;
 }
 
+// ---- test hook: bntseq.c's three helpers on a built genome, one thread per (rb, re, mid) of the
+// doubled text (0 <= rb <= re <= 2 l_pac, rb and mid below 2 l_pac, checked here before the launch):
+// rid_pos[i] = g_pos2rid(g_depos(rb)), rid_intv[i] = g_intv2rid(rb, re), clip[3 i ..] = g_fetch_clip's
+// (beg, end, rid) of the window [rb, re) around mid.  tests/test_gpu_genome.py::
+// test_rid_helpers_equal_plain_search.
+__global__ __launch_bounds__(256) void k_debug_g_rid(DevGenome G, const int64_t *__restrict__ rb,
+                                                     const int64_t *__restrict__ re, const int64_t *__restrict__ mid,
+                                                     int n, int32_t *__restrict__ rid_pos,
+                                                     int32_t *__restrict__ rid_intv, int64_t *__restrict__ clip) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int is_rev, rid;
+    rid_pos[i] = g_pos2rid(G, g_depos(G, rb[i], &is_rev));
+    rid_intv[i] = g_intv2rid(G, rb[i], re[i]);
+    int64_t b = rb[i], e = re[i];
+    g_fetch_clip(G, &b, mid[i], &e, &rid);
+    clip[3 * (int64_t)i] = b;
+    clip[3 * (int64_t)i + 1] = e;
+    clip[3 * (int64_t)i + 2] = rid;
+}
+extern "C" int af_debug_g_rid(const af_genome *g, const int64_t *rb, const int64_t *re, const int64_t *mid, int32_t n,
+                              int32_t *rid_pos, int32_t *rid_intv, int64_t *clip) {
+    const DevGenome *G = af_genome_dev(g);
+    if (!G || n < 1 || !rb || !re || !mid || !rid_pos || !rid_intv || !clip) return -1;
+    for (int i = 0; i < n; ++i)
+        if (rb[i] < 0 || rb[i] > re[i] || re[i] > G->N || rb[i] >= G->N || mid[i] < 0 || mid[i] >= G->N) return -1;
+    int64_t *din = nullptr, *dclip = nullptr;  // rb[n], re[n], mid[n]
+    int32_t *drid = nullptr;                   // rid_pos[n], rid_intv[n]
+    int rc = -1;
+    const size_t nb = sizeof(int64_t) * (size_t)n;
+    if (hipMalloc(&din, 3 * nb) == hipSuccess && hipMalloc(&dclip, 3 * nb) == hipSuccess &&
+        hipMalloc(&drid, sizeof(int32_t) * 2 * (size_t)n) == hipSuccess &&
+        hipMemcpy(din, rb, nb, hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(din + n, re, nb, hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(din + 2 * (size_t)n, mid, nb, hipMemcpyHostToDevice) == hipSuccess) {
+        hipLaunchKernelGGL(k_debug_g_rid, dim3((n + 255) / 256), dim3(256), 0, 0, *G, din, din + n, din + 2 * (size_t)n,
+                           n, drid, drid + n, dclip);
+        if (hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+            hipMemcpy(rid_pos, drid, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(rid_intv, drid + n, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(clip, dclip, 3 * nb, hipMemcpyDeviceToHost) == hipSuccess)
+            rc = 0;
+    }
+    (void)hipFree(din); (void)hipFree(dclip); (void)hipFree(drid);
+    return rc;
+}
+
 #ifdef AF_G_PROF
 static int32_t *h_gprof = nullptr;
 static int64_t h_gprof_cap = 0;

@@ -8,7 +8,11 @@ restatement (oracle/bwa_pe.c, FM mode) -- bit-exact.
   SAM record (flags, contigs, positions, CIGARs with -M hard clips, SEQ slices) on chimeric and
   plain reads with errors, indels and N;
 * S4 (`bwa mem -M genome fq1 fq2`, AF:188): every record of every pair, with the per-chunk
-  insert-size statistics, mate rescue and pairing.
+  insert-size statistics, mate rescue and pairing;
+* bntseq.c's contig rules (tests/boundary_world.py: 54 contigs from 1 base up, boundaries on a
+  bucket edge of the g_pos2rid table and 48 to a bucket, reads and pairs at every contig end and
+  across l_pac): the helpers against a plain search, the index, and every interval, region and
+  record on the default build and on each forced path.
 """
 import numpy as np
 import pytest
@@ -376,3 +380,173 @@ def test_pe_rescue_jobs_equal_oracle(world, monkeypatch, windows):
             assert msg is None, (r, msg)
     finally:
         g2.close()
+
+
+# ---- contig ends and the strand boundary (tests/boundary_world.py) --------------------------------
+def _regs_equal(ro, no, rg, ng):
+    assert np.array_equal(no, ng), np.nonzero(no != ng)[0][:10]
+    for r in range(len(no)):
+        for k in range(min(no[r], ro.shape[1])):
+            o = ro[r, k]
+            want = (o["rb"], o["re"], o["qb"], o["qe"], o["rid"], o["score"], o["truesc"], o["w"], o["seedcov"],
+                    o["seedlen0"])
+            assert tuple(int(v) for v in want) == tuple(int(v) for v in rg[r, k][:10]), (r, k)
+
+
+def _recs_equal(ro, no, rg, ng, what):
+    assert np.array_equal(no, ng), (what, np.nonzero(no != ng)[0][:10])
+    for r in range(len(no)):
+        msg = _rec_equal(ro[r], rg[r], min(no[r], 8))
+        assert msg is None, (what, r, msg)
+
+
+@pytest.fixture(scope="module", params=["A", "B"])
+def bworld(request):
+    """A boundary world (variant A: l_pac = 4 buckets; B: one base more), its reads and pairs, both
+    indexes and the oracle's answers, computed once."""
+    import boundary_world as bw
+    from anchored_fusion_amd.genome import GenomeIndex
+    w = bw.world(request.param)
+    og = oracle.OracleGenome(w.contigs)
+    reads, lens, meta = bw.junction_reads(w)
+    pairs, pmeta = bw.boundary_pairs(w)
+    plens = np.full(pairs.shape[0], pairs.shape[1], np.int32)
+    ref = dict(iv=og.intervals(reads, lens, threads=8), reg=og.regions(reads, lens, max_reg=64, threads=8),
+               se=og.align_se(reads, lens, id_base=0, threads=8), pe={})
+    for matesw in (50, 0):
+        pe = oracle.default_pe()
+        pe.max_matesw = matesw
+        ref["pe"][matesw] = og.align_pe(pairs, plens, pe=pe, pair_base=0, threads=8)
+    gg = GenomeIndex(w.contigs, device=0)
+    yield dict(w=w, og=og, gg=gg, reads=reads, lens=lens, meta=meta, pairs=pairs, plens=plens, pmeta=pmeta, ref=ref)
+    gg.close()
+
+
+def _forced(bworld, monkeypatch, env):
+    """The world's index on the default build, or a fresh one under a forced path's variable (read
+    when the context is made, or per call)."""
+    from anchored_fusion_amd.genome import GenomeIndex
+    if env is None:
+        return bworld["gg"], False
+    monkeypatch.setenv(*env)
+    return GenomeIndex(bworld["w"].contigs, device=0), True
+
+
+def test_rid_helpers_equal_plain_search(bworld):
+    """g_pos2rid (the 65,536-base bucket table of fmindex.hip k_ctg_bkt and its walk), g_intv2rid
+    and g_fetch_clip through the hook af_debug_g_rid, against numpy.searchsorted on the contig
+    offsets: every position within 2 of a contig start, of a bucket edge, of 0, l_pac and
+    2 l_pac - 1 on both strands; intervals of 1, 19 and 150 bases from each; the clip of
+    [p - 400, p + 400) around each (cut to the text as bwa cuts its windows first).  Exact."""
+    import ctypes
+    from anchored_fusion_amd import _lib
+    w, gg = bworld["w"], bworld["gg"]
+    lib = _lib.lib()
+    vp = ctypes.c_void_p
+    lib.af_debug_g_rid.restype = ctypes.c_int
+    lib.af_debug_g_rid.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp]
+    N = 2 * w.l_pac
+    assert gg.l_pac == w.l_pac
+    centers = np.concatenate([w.off[:-1], np.arange(0, w.l_pac + 1, 1 << 16), [0, w.l_pac, N - 1]])
+    p = (centers[:, None] + np.arange(-2, 3)[None, :]).reshape(-1)
+    p = np.unique(np.concatenate([p, N - 1 - p]))
+    p = p[(p >= 0) & (p < N)]
+    rb = np.concatenate([p, p, p, np.maximum(p - 400, 0)])
+    re = np.concatenate([np.minimum(p + 1, N), np.minimum(p + 19, N), np.minimum(p + 150, N), np.minimum(p + 400, N)])
+    mid = np.concatenate([p, p, p, p])
+    rb, re, mid = (np.ascontiguousarray(v, np.int64) for v in (rb, re, mid))
+    n = len(rb)
+    rid_pos = np.full(n, -9, np.int32)
+    rid_intv = np.full(n, -9, np.int32)
+    clip = np.full((n, 3), -9, np.int64)
+    assert lib.af_debug_g_rid(gg.g, rb.ctypes.data, re.ctypes.data, mid.ctypes.data, n, rid_pos.ctypes.data,
+                              rid_intv.ctypes.data, clip.ctypes.data) == 0
+    want_pos = w.rid_of(w.depos(rb))
+    bad = np.nonzero(rid_pos != want_pos)[0]
+    assert bad.size == 0, ("g_pos2rid", [(int(rb[i]), int(rid_pos[i]), int(want_pos[i])) for i in bad[:5]])
+    want_intv = w.intv2rid(rb, re)
+    bad = np.nonzero(rid_intv != want_intv)[0]
+    assert bad.size == 0, ("g_intv2rid",
+                           [(int(rb[i]), int(re[i]), int(rid_intv[i]), int(want_intv[i])) for i in bad[:5]])
+    assert (want_intv == -1).sum() > 100 and (want_intv == -2).sum() >= 10  # the cases are there
+    want_clip = np.stack(w.fetch_clip(rb, mid, re), 1)
+    bad = np.nonzero((clip != want_clip).any(1))[0]
+    assert bad.size == 0, ("g_fetch_clip", [(int(rb[i]), int(mid[i]), int(re[i]), clip[i].tolist(),
+                                             want_clip[i].tolist()) for i in bad[:5]])
+    # the argument checks answer before any launch
+    one = np.array([N], np.int64)
+    zero = np.zeros(1, np.int64)
+    out = np.zeros(3, np.int64)
+    for a, b, c in ((one, one, zero), (zero, zero, one), (zero, one + 1, zero), (zero - 1, zero, zero),
+                    (one - 1, zero, zero)):
+        assert lib.af_debug_g_rid(gg.g, a.ctypes.data, b.ctypes.data, c.ctypes.data, 1, out.ctypes.data,
+                                  out.ctypes.data, out.ctypes.data) == -1
+    assert lib.af_debug_g_rid(None, zero.ctypes.data, zero.ctypes.data, zero.ctypes.data, 1, out.ctypes.data,
+                              out.ctypes.data, out.ctypes.data) == -1
+
+
+def test_boundary_index_equals_oracle(bworld):
+    """54 contigs from 1 base up, l_pac a multiple of the bucket size (A) and one base past it (B):
+    text, primary and every suffix-array row equal the oracle's, and the GPU's text / SA /
+    occurrence table pass fm_checks.check_index."""
+    from fm_checks import check_index
+    w, og, gg = bworld["w"], bworld["og"], bworld["gg"]
+    assert gg.l_pac == og.l_pac == w.l_pac
+    T, sa, occ = gg.text(), gg.sa(), gg.occ()
+    assert np.array_equal(T, og.text())
+    assert gg.primary() == og.primary()
+    bad = np.nonzero(og.sa() != sa)[0]
+    assert bad.size == 0, f"{bad.size} suffix-array rows differ, first {bad[:5]}"
+    check_index(lambda a, n: T[a:a + n], lambda a, n: sa[a:a + n], lambda a, n: occ[a:a + n], gg.l_pac, gg.primary())
+
+
+@pytest.mark.parametrize("env", [None, ("AF_G_HEAVY_CHAINS", "1"), ("AF_G1_HEAVY_EXT", "1"), ("AF_G_CHAIN_ARR", "0")],
+                         ids=["default", "heavy_chains", "g1_wave", "kbtree"])
+def test_boundary_reads_equal_oracle(bworld, monkeypatch, env):
+    """S5 on reads laid across every contig boundary and across l_pac (boundary_world.
+    junction_reads): seed intervals, regions and records equal the oracle's on the default build and
+    with each path that computes or consumes the extension windows forced; the GPU's records also
+    stay inside their contigs and put every unique one-contig window at its origin."""
+    import boundary_world as bw
+    ref = bworld["ref"]
+    reads, lens = bworld["reads"], bworld["lens"]
+    gg, own = _forced(bworld, monkeypatch, env)
+    try:
+        ig, ng = gg.intervals(reads, lens)
+        _iv_sets_equal(ref["iv"][0], ref["iv"][1], ig, ng)
+        rg, ng = gg.regions(reads, lens, max_reg=64)
+        _regs_equal(ref["reg"][0], ref["reg"][1], rg, ng)
+        sg, ng = gg.align_se(reads, lens, id_base=0)
+        _recs_equal(ref["se"][0], ref["se"][1], sg, ng, "S5")
+        bw.check_se_records(bworld["w"], lens, bworld["meta"], sg, ng)
+        assert gg.stats()["cap_overflow"] == 0
+    finally:
+        if own:
+            gg.close()
+
+
+@pytest.mark.parametrize("env", [None, ("AF_G_PE_SPEC_WINDOWS", "1")], ids=["default", "rescue_jobs"])
+def test_boundary_pairs_equal_oracle(bworld, monkeypatch, env):
+    """S4 on pairs at contig ends (boundary_world.boundary_pairs), one chunk: every record equals
+    the oracle's with mate rescue on and off, in the pair's own walk and with the rescue windows
+    computed ahead as jobs; a mate at a contig's end is rescued inside that contig, none across a
+    boundary."""
+    import boundary_world as bw
+    from anchored_fusion_amd import _lib
+    pairs, plens = bworld["pairs"], bworld["plens"]
+    gg, own = _forced(bworld, monkeypatch, env)
+    try:
+        for matesw in (50, 0):
+            pe = _lib.default_pe()
+            pe.max_matesw = matesw
+            pg, ng = gg.align_pe(pairs, plens, pe=pe)
+            ro, no = bworld["ref"]["pe"][matesw]
+            _recs_equal(ro, no, pg, ng, ("S4", matesw))
+            bw.check_pe_records(bworld["w"], bworld["pmeta"], pg, ng, matesw > 0)
+            st = gg.stats()  # of this call
+            assert st["cap_overflow"] == 0
+            if env is not None and matesw:
+                assert st["pe_rescue_job_pairs"] > 500
+    finally:
+        if own:
+            gg.close()
